@@ -1,7 +1,17 @@
 """Learner throughput bench: QLearner.train on synthetic replay, MI355X, 1..8 GPUs (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--phases]]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
+
+A plain run does only what the headline figure needs: it builds the workload, runs W warm-up steps, times K steps,
+writes the outputs if `--dump-outputs DIR` is given and prints the JSON line (`roofline`, `cpu_baseline` and
+`rollout_baseline` null). `--full` adds everything else this file measures (below): the phase survey, the second
+timed region for the roofline entry, the PMC traffic lookup and the host baselines.
+
+`--dump-outputs DIR` writes what the last timed train() left its caller as DIR/<name>.npy (float32): the step's
+stats, the online and target parameters, the RMSprop state and the gradient buffers. Replay, weights and sampled ids
+are seeded, so two runs with the same arguments train on identical inputs.
 
 `--gpus N` means N ranks: launched without torch.distributed.run (WORLD_SIZE unset) and N > 1, the parent starts
 `torch.distributed.run --nproc-per-node N` as a child process before it touches the GPU and exits with its code;
@@ -15,7 +25,7 @@ RCCL). The replay (5000 episodes, SURVEY.md §8d recipe) lives in HBM; a step is
 full train(): id sampling on the host, fused gather, both unrolls, double-Q, mixer, loss, BPTT, clip, RMSprop,
 the episode-counted target update — nothing skipped.
 
-The JSON line also carries:
+With `--full` the JSON line also carries:
 * roofline: the dominant kernel (longest mean duration in an untimed 4-step phase survey) priced by its
   ALGORITHMIC fp32 flops per launch (DESIGN.md "Roofline") against the gfx950 fp32 peak; its average launch
   duration comes from HIP events on the learner's stream over a second timed region of the same K steps (the
@@ -377,6 +387,21 @@ def release_handles(*objs):
     th.cuda.synchronize()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, tensors):
+    """--dump-outputs: {name: device tensor} -> dirname/<name>.npy, float32, at most DUMP_LIMIT_BYTES in all (a
+    tensor over its equal share of that is cut to a fixed, seeded sample of its elements)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (4 * len(tensors))
+    for name, t in tensors.items():
+        v = np.ascontiguousarray(t.detach().reshape(-1).cpu().numpy(), dtype=np.float32)
+        if v.size > share:
+            v = v[np.sort(np.random.RandomState(0).choice(v.size, share, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), v)
+
+
 def coma_bench(a):
     """cfg5: COMALearner.train on coma_smac's batch of B = 8 episodes (MMM2 shape: 80 critic rows). N > 1 is strong
     scaling of that batch: every rank passes the same global sample, runs the critic's T dependent optimiser steps
@@ -415,17 +440,20 @@ def coma_bench(a):
         t = th.tensor([dt], dtype=th.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    learner.set_timing(True)
+    if a.dump_outputs and rank == 0:
+        Pa, Pc = learner.n_agent_params, learner.n_critic_params
+        dump_outputs(a.dump_outputs, {
+            "stats": learner._stats, "agent_params": learner._agent[:Pa], "critic_params": learner._critic[:Pc],
+            "target_critic_params": learner._tcritic[:Pc], "agent_square_avg": learner._asq[:Pa],
+            "critic_square_avg": learner._csq[:Pc], "agent_grad": learner._agrad[:Pa],
+            "critic_grad": learner._cgrad[:Pc]})
     chains = []
-    for k in range(min(a.steps, 20)):
-        step(k)
-        chains.append(learner.phase_times())
-    learner.set_timing(False)
-    chain_ms = float(np.mean([c["critic_chain"] for c in chains]))
-    Kc = S + O + 2 * n * A + n
-    R = B * n
-    step_flops = 2 * R * (2 * Kc * 128 + 3 * 128 * 128 + 2 * 128 * A)   # one critic step, fwd + bwd
-    achieved = step_flops / (chain_ms * 1e-3 / T) / 1e12
+    if a.full:   # critic chain timing: further steps with HIP events around the learner's phases
+        learner.set_timing(True)
+        for k in range(min(a.steps, 20)):
+            step(k)
+            chains.append(learner.phase_times())
+        learner.set_timing(False)
     value = B * T * n * a.steps / dt
     if rank != 0:
         from pymarl_amd.learners.dp import SharedComm
@@ -433,12 +461,28 @@ def coma_bench(a):
         SharedComm.free()
         dist.destroy_process_group()
         return
-    cpu = None if (a.no_cpu_baseline or world > 1) else coma_cpu_baseline(a.config, data)
-    # PMC bytes of the whole persistent chain launch, per critic step like `achieved` and `launch_ms`
-    traffic, traffic_src = (pmc_traffic(a.config, "coma_chain") if learner.critic_path() == "chain"
-                            else (None, "PMC covers the persistent chain only"))
-    if traffic is not None:
-        traffic, traffic_src = traffic / T, traffic_src + f"; the chain launch's bytes / T = {T} critic steps"
+    cpu = roof = None
+    if a.full:
+        chain_ms = float(np.mean([c["critic_chain"] for c in chains]))
+        Kc = S + O + 2 * n * A + n
+        R = B * n
+        step_flops = 2 * R * (2 * Kc * 128 + 3 * 128 * 128 + 2 * 128 * A)   # one critic step, fwd + bwd
+        achieved = step_flops / (chain_ms * 1e-3 / T) / 1e12
+        cpu = None if (a.no_cpu_baseline or world > 1) else coma_cpu_baseline(a.config, data)
+        # PMC bytes of the whole persistent chain launch, per critic step like `achieved` and `launch_ms`
+        traffic, traffic_src = (pmc_traffic(a.config, "coma_chain") if learner.critic_path() == "chain"
+                                else (None, "PMC covers the persistent chain only"))
+        if traffic is not None:
+            traffic, traffic_src = traffic / T, traffic_src + f"; the chain launch's bytes / T = {T} critic steps"
+        roof = {"bound": "mfma", "kernel": ("coma_chain_kernel (one persistent launch, T critic steps)"
+                                            if learner.critic_path() == "chain"
+                                            else "critic step chain (l1 + head + wgrad, x T)"),
+                "critic_path": learner.critic_path(),
+                "achieved": achieved, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": achieved / FP32_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+                "launch_ms": chain_ms / T,
+                "flops_per_launch": step_flops,
+                "phases_ms": {k: float(np.mean([c[k] for c in chains])) for k in chains[0]}}
     line = {
         "metric": METRIC, "value": value, "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -449,16 +493,7 @@ def coma_bench(a):
                    "coma_dp_mode": learner.dp_mode(B)},
         "dist": dist_info(world, learner, "critic replicated on the whole batch, actor sharded: all_reduce(sum) of "
                                           "the agent [grads | sums] buffer once per train"),
-        "roofline": {"bound": "mfma", "kernel": ("coma_chain_kernel (one persistent launch, T critic steps)"
-                                                 if learner.critic_path() == "chain"
-                                                 else "critic step chain (l1 + head + wgrad, x T)"),
-                     "critic_path": learner.critic_path(),
-                     "achieved": achieved, "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / FP32_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                     "launch_ms": chain_ms / T,
-                     "flops_per_launch": step_flops,
-                     "phases_ms": {k: float(np.mean([c[k] for c in chains])) for k in chains[0]}},
-        "cpu_baseline": cpu,
+        "full": a.full, "roofline": roof, "cpu_baseline": cpu,
     }
     print(json.dumps(line), flush=True)
     release_handles(learner, mac)
@@ -498,11 +533,19 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--phases", action="store_true", help="print every phase's mean ms to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the phase survey, the roofline timing and the host baselines (module doc)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step left its caller as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the host baselines")
+    ap.add_argument("--phases", action="store_true", help="with --full: print every phase's mean ms to stderr")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if a.phases and not a.full:
+        raise SystemExit("--phases prints the phase survey, which only a --full run takes")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and a.gpus > 1:
         sys.exit(launch_ranks(a))
@@ -537,19 +580,21 @@ def main():
     for k in range(max(1, a.warmup)):
         step(k)
     th.cuda.synchronize()
-    # phase survey (untimed): which kernel dominates
-    names = learner.phase_names()
-    learner.set_timing(slots=4)
-    for k in range(4):
-        step(k)
-    th.cuda.synchronize()
-    survey = learner.phase_times()
-    dominant = max(survey, key=survey.get)
-    plan = learner.last_plan()   # the kernel variants the timed steps run (row tiles, fused kernels, hypernet, mixer)
-    fused_fwd = survey.get("fc1", 0.0) == 0.0     # the fused agent forward carries fc1 / W_ih / fc2
-    fused_bwd = survey.get("dx1", 0.0) == 0.0     # the fused BPTT carries dX1 / dW1
-    # no hypernet launch of its own under QMIX: the forward carries it
-    hyp_in_fwd = mixer == "qmix" and survey.get("hyper", 0.0) == 0.0
+    if a.full:
+        # phase survey (untimed): which kernel dominates
+        learner.set_timing(slots=4)
+        for k in range(4):
+            step(k)
+        th.cuda.synchronize()
+        survey = learner.phase_times()
+        dominant = max(survey, key=survey.get)
+        # the kernel variants the timed steps run (row tiles, fused kernels, hypernet, mixer)
+        plan = learner.last_plan()
+        fused_fwd = survey.get("fc1", 0.0) == 0.0     # the fused agent forward carries fc1 / W_ih / fc2
+        fused_bwd = survey.get("dx1", 0.0) == 0.0     # the fused BPTT carries dX1 / dW1
+        # no hypernet launch of its own under QMIX: the forward carries it
+        hyp_in_fwd = mixer == "qmix" and survey.get("hyper", 0.0) == 0.0
+        learner.set_timing(slots=0)
 
     def timed():
         barrier()
@@ -562,13 +607,18 @@ def main():
         return time.perf_counter() - t0
 
     # timed region 1 -> value: no events in the stream
-    learner.set_timing(slots=0)
     dt = timed()
-    # timed region 2 -> roofline: the same K steps with HIP events (learner stream) around the dominant kernel
-    learner.set_timing(slots=min(a.steps, 4096), phases=[dominant])
-    timed()
-    dom_ms = learner.phase_times()[dominant]
-    learner.set_timing(slots=0)
+    if a.dump_outputs and rank == 0:
+        P = learner.n_params
+        dump_outputs(a.dump_outputs, {"stats": learner._stats, "params": learner._online[:P],
+                                      "target_params": learner._target[:P], "square_avg": learner._sq[:P],
+                                      "grad": learner._grad[:P]})
+    if a.full:
+        # timed region 2 -> roofline: the same K steps with HIP events (learner stream) around the dominant kernel
+        learner.set_timing(slots=min(a.steps, 4096), phases=[dominant])
+        timed()
+        dom_ms = learner.phase_times()[dominant]
+        learner.set_timing(slots=0)
     if world > 1:
         t = th.tensor([dt], dtype=th.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -577,20 +627,21 @@ def main():
     samples = B * T * n * world * a.steps
     value = samples / dt
     if rank == 0:
-        if a.phases:
-            print(json.dumps({"phase_ms": survey}), file=sys.stderr)
-        fl = algorithmic_flops(dominant, n, A, O, S, T, B, mixer=mixer, fused_fwd=fused_fwd, fused_bwd=fused_bwd,
-                               hyp_in_fwd=hyp_in_fwd)
-        achieved = (fl / (dom_ms * 1e-3) / 1e12) if (fl and dom_ms > 0) else None
-        traffic, traffic_src = pmc_traffic(a.config, dominant)
-        roof = {"bound": "mfma", "kernel": dominant, "achieved": achieved, "peak": FP32_PEAK_TFLOPS,
-                "unit": "TFLOP/s", "frac": (achieved / FP32_PEAK_TFLOPS) if achieved else None,
-                "traffic": traffic, "traffic_source": traffic_src, "launch_ms": dom_ms, "flops_per_launch": fl,
-                "fused": {"fwd": fused_fwd, "bwd": fused_bwd, "hyp_in_fwd": hyp_in_fwd}, "plan": plan}
-        cpu = rollout = None
-        if world == 1 and not a.no_cpu_baseline:
-            cpu = cpu_baseline(a.config, data)
-            rollout = rollout_baseline(a.config, device)
+        roof = cpu = rollout = None
+        if a.full:
+            if a.phases:
+                print(json.dumps({"phase_ms": survey}), file=sys.stderr)
+            fl = algorithmic_flops(dominant, n, A, O, S, T, B, mixer=mixer, fused_fwd=fused_fwd,
+                                   fused_bwd=fused_bwd, hyp_in_fwd=hyp_in_fwd)
+            achieved = (fl / (dom_ms * 1e-3) / 1e12) if (fl and dom_ms > 0) else None
+            traffic, traffic_src = pmc_traffic(a.config, dominant)
+            roof = {"bound": "mfma", "kernel": dominant, "achieved": achieved, "peak": FP32_PEAK_TFLOPS,
+                    "unit": "TFLOP/s", "frac": (achieved / FP32_PEAK_TFLOPS) if achieved else None,
+                    "traffic": traffic, "traffic_source": traffic_src, "launch_ms": dom_ms, "flops_per_launch": fl,
+                    "fused": {"fwd": fused_fwd, "bwd": fused_bwd, "hyp_in_fwd": hyp_in_fwd}, "plan": plan}
+            if world == 1 and not a.no_cpu_baseline:
+                cpu = cpu_baseline(a.config, data)
+                rollout = rollout_baseline(a.config, device)
         bytes_per_sample = (O * 4 + (S * 4) / n + 8 + A * 4 + (4 + 1 + 8) / n)   # read-once replay bytes
         line = {
             "metric": METRIC, "value": value, "unit": "samples/s", "n_gpus": world, "steps": a.steps,
@@ -600,6 +651,7 @@ def main():
                        "state_dim": S, "episode_limit": T, "batch_per_gpu": B, "global_batch": B * world,
                        "replay_episodes": buf.buffer_size, "parallelism": f"dp{world}"},
             "dist": dist_info(world, learner),
+            "full": a.full,
             "roofline": roof,
             "hbm_roofline_whole_step": {"achieved_GBs": value * bytes_per_sample / 1e9, "peak_GBs": HBM_PEAK_GBS,
                                         "frac": value * bytes_per_sample / 1e9 / HBM_PEAK_GBS},

@@ -38,7 +38,7 @@ done
 for i in 1 2; do
   for v in $VS; do
     E=""; [ $v = base ] && E="MQ_LEARNER_LIB=$BASE"; [ $v = alt ] && E="MQ_LEARNER_LIB=$ALT"
-    env $E timeout -k 10 200 python bench.py --config cfg5 --steps 10 --warmup 2 --no-cpu-baseline > $O/${T}_bench_${v}_$i.json 2> $O/${T}_bench_${v}_$i.err || exit 1
+    env $E timeout -k 10 200 python bench.py --config cfg5 --steps 10 --warmup 2 --full --no-cpu-baseline > $O/${T}_bench_${v}_$i.json 2> $O/${T}_bench_${v}_$i.err || exit 1
     python -c "import json;d=json.load(open('$O/${T}_bench_${v}_$i.json'));print('  bench $v $i', round(d['ms_per_step'],4), d['roofline'].get('phases_ms'))"
   done
 done

@@ -26,25 +26,25 @@ for P in "$@"; do
     cfg*)
       CFG=${P%%:*}; MODE=${P#*:}; [ "$MODE" = "$P" ] && MODE=full
       case $CFG in cfg3|cfg5) STEPS=20 ;; *) STEPS=50 ;; esac
-      timeout -k 10 400 python bench.py --config $CFG --steps $STEPS --warmup 5 --phases > $O/bench_${TAG}_${CFG}.json 2> $O/bench_${TAG}_${CFG}.err || { tail -5 $O/bench_${TAG}_${CFG}.err; exit 1; }
+      timeout -k 10 400 python bench.py --config $CFG --steps $STEPS --warmup 5 --full --phases > $O/bench_${TAG}_${CFG}.json 2> $O/bench_${TAG}_${CFG}.err || { tail -5 $O/bench_${TAG}_${CFG}.err; exit 1; }
       summ $O/bench_${TAG}_${CFG}.json $CFG || exit 1
       grep phase $O/bench_${TAG}_${CFG}.err | tail -3
       [ "$MODE" = bench ] && continue
       if [ "$CFG" = cfg2 ]; then
-        timeout -k 10 300 python bench.py > $O/bench_${TAG}_driver_cmd.json 2> $O/bench_${TAG}_driver_cmd.err || exit 1
+        timeout -k 10 300 python bench.py --full > $O/bench_${TAG}_driver_cmd.json 2> $O/bench_${TAG}_driver_cmd.err || exit 1
         summ $O/bench_${TAG}_driver_cmd.json driver_cmd || exit 1
       fi
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_${CFG} -o run -- python $R/bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline > $O/prof_${TAG}_${CFG}.log 2>&1) || exit 1
       [ "$MODE" = prof ] && continue
       bash scripts/gpu_counters.sh $TAG $CFG || exit 1 ;;
     gloo2)
-      MQ_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 20 --warmup 3 > $O/bench_${TAG}_gloo2_cfg2.json 2> $O/bench_${TAG}_gloo2_cfg2.err || exit 1
-      MQ_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29532 bench.py --config cfg5 --gpus 2 --steps 3 --warmup 1 > $O/bench_${TAG}_gloo2_cfg5.json 2> $O/bench_${TAG}_gloo2_cfg5.err || exit 1
+      MQ_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 20 --warmup 3 --full > $O/bench_${TAG}_gloo2_cfg2.json 2> $O/bench_${TAG}_gloo2_cfg2.err || exit 1
+      MQ_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29532 bench.py --config cfg5 --gpus 2 --steps 3 --warmup 1 --full > $O/bench_${TAG}_gloo2_cfg5.json 2> $O/bench_${TAG}_gloo2_cfg5.err || exit 1
       echo "gloo rehearsals done" ;;
     traffic)
-      timeout -k 10 300 python bench.py > $O/bench_${TAG}_traffic_cfg2.json 2> $O/bench_${TAG}_traffic_cfg2.err || exit 1
+      timeout -k 10 300 python bench.py --full > $O/bench_${TAG}_traffic_cfg2.json 2> $O/bench_${TAG}_traffic_cfg2.err || exit 1
       for c in cfg3 cfg4 cfg5; do
-        timeout -k 10 300 python bench.py --config $c --steps 10 --warmup 3 > $O/bench_${TAG}_traffic_$c.json 2> $O/bench_${TAG}_traffic_$c.err || exit 1
+        timeout -k 10 300 python bench.py --config $c --steps 10 --warmup 3 --full > $O/bench_${TAG}_traffic_$c.json 2> $O/bench_${TAG}_traffic_$c.err || exit 1
       done
       for c in cfg2 cfg3 cfg4 cfg5; do summ $O/bench_${TAG}_traffic_$c.json $c; done ;;
     *) echo "unknown part $P"; exit 2 ;;
