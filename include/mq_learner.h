@@ -54,6 +54,14 @@ typedef struct mq_config {
   int32_t max_seq;           /* most stored steps per episode (episode_limit + 1) */
   float huber_delta;         /* TD loss: 0 = masked L2 (q_learner.py:96-97, default); > 0 = masked Huber with this
                                 delta, an opt-in the reference lacks (not pinned by its goldens) */
+  float td_lambda;           /* TD target: 0 = the one-step target r + gamma (1 - term) Q'_tot(t+1) (q_learner.py:86,
+                                default; the kernels of that path run as they always did); in (0, 1] = TD(lambda)
+                                returns, build_td_lambda_targets (rl_utils.py:4-14) over the target network's mixed
+                                values with the learner's mask, as COMALearner applies it: an opt-in the reference's
+                                Q learner lacks. The mixer tail then runs as three launches (targets, the backward
+                                scan over t, loss + mixer backward). Outside [0, 1] or NaN: MQ_ERR_ARG; so is a
+                                max_seq whose scan inputs, (max_seq - 1) * (k + 3) floats with k = 1 (no mixer:
+                                n_agents), pass 64 KB of LDS. */
 } mq_config;
 
 /* A batch of episodes as the learner reads it: the replay storage (reference scheme dtypes, episode-major
@@ -127,7 +135,10 @@ int mq_update_targets(mq_handle* h, void* stream);
 
 /* Copy an intermediate of the last mq_forward_backward into dst (device): 0 = online mac_out [t][b*n+a][A],
  * 1 = target mac_out (same layout), 2 = dQ/dchosen [t][b*n+a] (unnormalised), 3 = online relu(fc1) activations
- * [t][b*n+a][64]. Returns element count in *count. */
+ * [t][b*n+a][64]. Returns element count in *count.
+ * After a step that ran the TD(lambda) passes (mq_plan.td_lambda = 1; MQ_ERR_STATE otherwise): 4 = y', the target
+ * network's mixed value at step t + 1, as [t][b] (no mixer: [t][b*n+a], one value per agent), t < t_len - 1;
+ * 5 = the lambda targets in the same layout. */
 int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, void* stream);
 
 /* BasicMAC.forward(ep_batch, t) for every episode of `batch`: h_in/h_out [batch*n][64] (h_in may equal
@@ -163,6 +174,9 @@ typedef struct mq_plan {
   int32_t tiles;         /* 1: the row-tile MFMA forward / BPTT of large batches (gru_fwd_tile / gru_bwd_tile);
                             fused_fwd / fused_bwd / rw_* are then 0 */
   int32_t dwh;           /* QMIX dW_hyper: beside reduction pass 1 (0) or appended to the fused BPTT's grid (1) */
+  int32_t td_lambda;     /* 1: the mixer tail ran as the TD(lambda) passes (mq_config.td_lambda > 0, or MQ_PLAN
+                            lambda_path=1, which runs them at td_lambda = 0 too: the one-step target through the scan,
+                            for A/B runs and tests); `mix` names the variant of both mixer passes */
 } mq_plan;
 int mq_last_plan(const mq_handle* h, mq_plan* out);
 

@@ -53,6 +53,7 @@ class MQConfig(ctypes.Structure):
         ("obs_agent_id", ctypes.c_int32), ("gamma", ctypes.c_float), ("lr", ctypes.c_float),
         ("optim_alpha", ctypes.c_float), ("optim_eps", ctypes.c_float), ("grad_norm_clip", ctypes.c_float),
         ("max_batch", ctypes.c_int32), ("max_seq", ctypes.c_int32), ("huber_delta", ctypes.c_float),
+        ("td_lambda", ctypes.c_float),
     ]
 
 
@@ -79,7 +80,7 @@ class MCConfig(ctypes.Structure):
 
 class MQPlan(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("rows", "fused_fwd", "rw_fwd", "fused_bwd", "rw_bwd", "inline_ids",
-                                               "hyper", "mix", "tiles", "dwh")]
+                                               "hyper", "mix", "tiles", "dwh", "td_lambda")]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}

@@ -14,6 +14,24 @@ namespace mq {
 MQ_DEV float sgnf(float x) { return (float)((x > 0.0f) - (x < 0.0f)); }
 MQ_DEV float eluf(float x) { return x > 0.0f ? x : expm1f(x); }
 
+// The mixer tail's passes. MIX_ONE_STEP is the reference's path (q_learner.py:86), one launch. TD(lambda) targets
+// (mq_config.td_lambda) are a backward recurrence over t, so the tail splits in two around td_lambda_kernel
+// (td_lambda_kernel.hpp): MIX_LAMBDA_TARGETS does the double-Q selection and the target-side mix only and stores
+// y'[m] (YT: [m], or [m][n] without a mixer); MIX_LAMBDA_LOSS does the online side, the loss and the mixer backward
+// with target = G[m], the scan's output, in place of r + gamma (1 - term) y'.
+enum { MIX_ONE_STEP = 0, MIX_LAMBDA_TARGETS = 1, MIX_LAMBDA_LOSS = 2 };
+
+// The lambda target of row m on this lane (VDN: one per row; no mixer: one per agent lane).
+MQ_DEV float lambda_target(const float* __restrict__ G, int mixer, bool valid, int m, int n, int lane) {
+  if (!valid) return 0.0f;
+  if (mixer == MQ_MIXER_NONE) return lane < n ? G[(int64_t)m * n + lane] : 0.0f;
+  return G[m];
+}
+
+// The two lambda passes take (YT, G) as trailing kernel arguments; the one-step kernels take none (LAM is empty), so
+// their argument block is the one they always had.
+MQ_DEV void lambda_args(float*& YT, const float*& G, float* yt, const float* g) { YT = yt; G = g; }
+
 struct MixOut {
   float y, pre, hid, wf_raw, hv;   // lane-e intermediates of the online mixer (QMIX)
 };
@@ -55,9 +73,13 @@ constexpr int MIXS_MAX = 1024;   // n * A staged per item
 constexpr int MIXS_NPT = MIXS_MAX / 256;
 inline bool mix_stream_ok(int n, int A) { return n * A <= MIXS_MAX; }
 
-template <bool STREAM>
+template <bool STREAM, int MODE = MIX_ONE_STEP, typename... LAM>
 __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* __restrict__ P0,
-                                                  const float* __restrict__ P1, Lay L, Work w, int32_t* curmax_out) {
+                                                  const float* __restrict__ P1, Lay L, Work w, int32_t* curmax_out,
+                                                  LAM... lam) {
+  float* YT = nullptr;
+  const float* G = nullptr;
+  if constexpr (MODE != MIX_ONE_STEP) lambda_args(YT, G, lam...);
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + wv;
   const int n = d.n, A = d.A, E = d.E, R = d.R, NH = d.NH;
@@ -79,14 +101,19 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
   float chosen = 0.0f, tmax = 0.0f;
   // the transition's mask / reward / terminated words, independent of the selection: in flight with it
   float mask = 0.0f, rew = 0.0f, term = 0.0f;
-  if (valid) {
+  if (MODE != MIX_LAMBDA_TARGETS && valid) {
     const int64_t slot = ep * d.t_stride + t;
     mask = (float)rp.filled[slot];
     if (t > 0) mask *= 1.0f - (float)rp.term[slot - 1];   // q_learner.py:42-43
     rew = rp.reward[slot];
     term = (float)rp.term[slot];
   }
-  if constexpr (STREAM) {
+  if constexpr (MODE == MIX_LAMBDA_LOSS) {   // the chosen-action values only: pass A made the selection
+    if (valid && lane < n) {
+      const int at = (int)rp.actions[(ep * d.t_stride + t) * n + lane];
+      chosen = Qon[((int64_t)t * R + b * n + lane) * A + at];
+    }
+  } else if constexpr (STREAM) {
     __shared__ float qm[4 * MIXS_MAX];      // the four items' masked selection rows [item][agent][action]
     __shared__ uint8_t avs[4 * MIXS_MAX];   // their avail bits
     const int nA = n * A;
@@ -95,7 +122,8 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
     int32_t avv[4][MIXS_NPT];
     // the agent lane's action first (its chosen value is one more round trip), then every staging load of the block
     // (avail as int32 here: per-element bit extraction from mq_replay.avail_bits measured slower, 74 vs 70 us)
-    const int at = (valid && lane < n) ? (int)rp.actions[(ep * d.t_stride + t) * n + lane] : 0;
+    const int at = (MODE != MIX_LAMBDA_TARGETS && valid && lane < n) ? (int)rp.actions[(ep * d.t_stride + t) * n + lane]
+                                                                     : 0;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int mi = min((int)blockIdx.x * 4 + it, d.M - 1);
@@ -109,7 +137,7 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
         avv[it][k] = arow[e];
       }
     }
-    if (valid && lane < n) chosen = Qon[((int64_t)t * R + b * n + lane) * A + at];
+    if (MODE != MIX_LAMBDA_TARGETS && valid && lane < n) chosen = Qon[((int64_t)t * R + b * n + lane) * A + at];
 #pragma unroll
     for (int it = 0; it < 4; ++it)
 #pragma unroll
@@ -139,8 +167,10 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
   if (valid && lane < n) {
     const int r = b * n + lane;
     const int64_t slot = ep * d.t_stride + t;
-    const int at = (int)rp.actions[slot * n + lane];
-    chosen = Qon[((int64_t)t * R + r) * A + at];
+    if constexpr (MODE != MIX_LAMBDA_TARGETS) {
+      const int at = (int)rp.actions[slot * n + lane];
+      chosen = Qon[((int64_t)t * R + r) * A + at];
+    }
     const float* qn = Qon + ((int64_t)(t + 1) * R + r) * A;
     const float* qt = Qtg + ((int64_t)(t + 1) * R + r) * A;
     const int32_t* av = rp.avail + ((slot + 1) * n + lane) * (int64_t)A;
@@ -176,6 +206,21 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
   tms[wv][lane] = tmax;
   __syncthreads();
 
+  if constexpr (MODE == MIX_LAMBDA_TARGETS) {   // y'[m]: the target net's mixed value at step t + 1, nothing else
+    if (d.mixer == MQ_MIXER_QMIX) {
+      const float* htg = w.HYP + ((int64_t)d.M + m) * NH;
+      if (valid) {
+        const float yt = qmix_fwd_lane(htg, tms[wv], P1 + L.o[MQ_P_V2_W], P1[L.o[MQ_P_V2_B]], n, E, lane, nullptr);
+        if (lane == 0) YT[m] = yt;
+      }
+    } else if (d.mixer == MQ_MIXER_VDN) {
+      const float yt = wave_sum(lane < n ? tmax : 0.0f);
+      if (valid && lane == 0) YT[m] = yt;
+    } else if (valid && lane < n) {
+      YT[(int64_t)m * n + lane] = tmax;
+    }
+    return;
+  }
   const float gamma = d.gamma;
   if (d.mixer == MQ_MIXER_QMIX) {
     const float* hon = w.HYP + (int64_t)m * NH;
@@ -186,11 +231,13 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
     float y = 0.0f, yt = 0.0f;
     if (valid) {
       y = qmix_fwd_lane(hon, chs[wv], V2w0, P0[L.o[MQ_P_V2_B]], n, E, lane, &k);
-      yt = qmix_fwd_lane(htg, tms[wv], V2w1, P1[L.o[MQ_P_V2_B]], n, E, lane, nullptr);
+      if constexpr (MODE == MIX_ONE_STEP)
+        yt = qmix_fwd_lane(htg, tms[wv], V2w1, P1[L.o[MQ_P_V2_B]], n, E, lane, nullptr);
     } else {
       k.y = k.pre = k.hid = k.wf_raw = k.hv = 0.0f;
     }
-    const float target = rew + gamma * (1.0f - term) * yt;   // q_learner.py:86
+    float target = rew + gamma * (1.0f - term) * yt;   // q_learner.py:86
+    if constexpr (MODE == MIX_LAMBDA_LOSS) target = valid ? G[m] : 0.0f;
     const float td = y - target;
     const float mtd = td * mask;
     l2 = td_loss(mtd, d.huber); msk = mask; abs_ = fabsf(mtd); qs = y * mask; tg = target * mask;
@@ -239,7 +286,8 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
       y = chosen;
       yt = tmax;
     }
-    const float target = rew + gamma * (1.0f - term) * yt;
+    float target = rew + gamma * (1.0f - term) * yt;
+    if constexpr (MODE == MIX_LAMBDA_LOSS) target = lambda_target(G, d.mixer, valid, m, n, lane);
     const float td = y - target;
     const float mtd = td * mask;
     const float dy = td_dy(mtd, mask, d.huber);
@@ -296,10 +344,13 @@ struct alignas(16) MixScratch {
   float w1s[MN][65];   // |hyper_w_1| rows of the online mixer, for dLoss/dchosen
 };
 
-template <int MA, int MN>
+template <int MA, int MN, int MODE = MIX_ONE_STEP>
 MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__ P0, const float* __restrict__ P1,
                          const Lay& L, const Work& w, int32_t* curmax_out, int m, int lane, const float* hon,
-                         const float* htg, MixScratch<MN>& sc, float* red_slot, float* v2_slot) {
+                         const float* htg, MixScratch<MN>& sc, float* red_slot, float* v2_slot,
+                         float* __restrict__ YT, const float* __restrict__ G) {
+  constexpr bool ONLINE = MODE != MIX_LAMBDA_TARGETS;   // chosen values, online mix, loss, mixer backward
+  constexpr bool TARGET = MODE != MIX_LAMBDA_LOSS;      // double-Q selection and the target-side mix
   const int n = d.n, A = d.A, E = d.E, R = d.R, NH = d.NH;
   const bool qmix = d.mixer == MQ_MIXER_QMIX;
   float l2 = 0.0f, msk = 0.0f, abs_ = 0.0f, qs = 0.0f, tg = 0.0f;
@@ -322,18 +373,20 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
   float qsel[MA], qtr[MA];
   int32_t avr[MA];
   if (agent_lane) {
-    at = (int)rp.actions[slot * n + lane];
-    const float* qn = Qon + ((int64_t)(t + 1) * R + r) * A;
-    const float* qt = Qtg + ((int64_t)(t + 1) * R + r) * A;
-    const float* qs_row = d.double_q ? qn : qt;
-    const int32_t* av = rp.avail + ((slot + 1) * n + lane) * (int64_t)A;
-    const uint64_t abits = rp.avail_bits ? rp.avail_bits[(slot + 1) * n + lane] : 0;
+    if constexpr (ONLINE) at = (int)rp.actions[slot * n + lane];
+    if constexpr (TARGET) {
+      const float* qn = Qon + ((int64_t)(t + 1) * R + r) * A;
+      const float* qt = Qtg + ((int64_t)(t + 1) * R + r) * A;
+      const float* qs_row = d.double_q ? qn : qt;
+      const int32_t* av = rp.avail + ((slot + 1) * n + lane) * (int64_t)A;
+      const uint64_t abits = rp.avail_bits ? rp.avail_bits[(slot + 1) * n + lane] : 0;
 #pragma unroll
-    for (int u = 0; u < MA; ++u) {
-      const int a = min(u, A - 1);
-      qsel[u] = qs_row[a];
-      qtr[u] = qt[a];
-      avr[u] = rp.avail_bits ? (int32_t)((abits >> a) & 1u) : av[a];
+      for (int u = 0; u < MA; ++u) {
+        const int a = min(u, A - 1);
+        qsel[u] = qs_row[a];
+        qtr[u] = qt[a];
+        avr[u] = rp.avail_bits ? (int32_t)((abits >> a) & 1u) : av[a];
+      }
     }
   }
   const bool e_lane = qmix && valid && lane < E;
@@ -341,29 +394,32 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
   if (e_lane) {
 #pragma unroll
     for (int ag = 0; ag < MN; ++ag) {
-      won[ag] = hon[min(ag, n - 1) * E + lane];
-      wtg[ag] = htg[min(ag, n - 1) * E + lane];
+      if constexpr (ONLINE) won[ag] = hon[min(ag, n - 1) * E + lane];
+      if constexpr (TARGET) wtg[ag] = htg[min(ag, n - 1) * E + lane];
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {   // hyper_w_final, hyper_b_1, V.0 outputs
-      xon[k] = hon[n * E + k * E + lane];
-      xtg[k] = htg[n * E + k * E + lane];
+      if constexpr (ONLINE) xon[k] = hon[n * E + k * E + lane];
+      if constexpr (TARGET) xtg[k] = htg[n * E + k * E + lane];
     }
-    v2w0 = P0[L.o[MQ_P_V2_W] + lane];
-    v2w1 = P1[L.o[MQ_P_V2_W] + lane];
+    if constexpr (ONLINE) v2w0 = P0[L.o[MQ_P_V2_W] + lane];
+    if constexpr (TARGET) v2w1 = P1[L.o[MQ_P_V2_W] + lane];
   }
   float mask = 0.0f, rew = 0.0f, term = 0.0f;
-  if (valid) {
+  if (ONLINE && valid) {
     mask = (float)rp.filled[slot];
     if (t > 0) mask *= 1.0f - (float)rp.term[slot - 1];   // q_learner.py:42-43
     rew = rp.reward[slot];
     term = (float)rp.term[slot];
   }
-  const float v2b0 = qmix ? P0[L.o[MQ_P_V2_B]] : 0.0f, v2b1 = qmix ? P1[L.o[MQ_P_V2_B]] : 0.0f;
+  const float v2b0 = (ONLINE && qmix) ? P0[L.o[MQ_P_V2_B]] : 0.0f, v2b1 = (TARGET && qmix) ? P1[L.o[MQ_P_V2_B]] : 0.0f;
   // ---- chosen value and double-Q selection (q_learner.py:55, 68-78), first index on ties
   float chosen = 0.0f, tmax = 0.0f;
+  if constexpr (!TARGET) {
+    if (agent_lane) chosen = Qon[((int64_t)t * R + r) * A + at];
+  } else
   if (agent_lane) {
-    chosen = Qon[((int64_t)t * R + r) * A + at];
+    if constexpr (ONLINE) chosen = Qon[((int64_t)t * R + r) * A + at];
     float best = 0.0f;
     int cur = 0;
 #pragma unroll
@@ -385,11 +441,33 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
   }
   sc.chs[lane] = chosen;
   sc.tms[lane] = tmax;
-  if (e_lane) {
+  if (ONLINE && e_lane) {
 #pragma unroll
     for (int ag = 0; ag < MN; ++ag) sc.w1s[ag][lane] = fabsf(won[ag]);
   }
   __syncthreads();
+  if constexpr (!ONLINE) {   // y'[m] only: qmix_fwd_lane's arithmetic on the target net, as below
+    if (qmix) {
+      float prod_t = 0.0f, vt_t = 0.0f;
+      if (e_lane) {
+        float acc_t = 0.0f;
+#pragma unroll
+        for (int ag = 0; ag < MN; ++ag)
+          if (ag < n) acc_t = fmaf(sc.tms[ag], fabsf(wtg[ag]), acc_t);
+        const float pre_t = acc_t + xtg[1];
+        prod_t = eluf(pre_t) * fabsf(xtg[0]);
+        vt_t = fmaxf(xtg[2], 0.0f) * v2w1;
+      }
+      const float yt = wave_sum(prod_t) + (wave_sum(vt_t) + v2b1);
+      if (valid && lane == 0) YT[m] = yt;
+    } else if (d.mixer == MQ_MIXER_VDN) {
+      const float yt = wave_sum(lane < n ? tmax : 0.0f);
+      if (valid && lane == 0) YT[m] = yt;
+    } else if (agent_lane) {
+      YT[(int64_t)m * n + lane] = tmax;
+    }
+    return;
+  }
   const float gamma = d.gamma;
   if (qmix) {
     // QMIX forward of both nets (qmix_fwd_lane's arithmetic, operands from registers)
@@ -402,22 +480,25 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
         for (int ag = 0; ag < MN; ++ag) {
           if (ag < n) {
             acc = fmaf(sc.chs[ag], fabsf(won[ag]), acc);
-            acc_t = fmaf(sc.tms[ag], fabsf(wtg[ag]), acc_t);
+            if constexpr (TARGET) acc_t = fmaf(sc.tms[ag], fabsf(wtg[ag]), acc_t);
           }
         }
         pre = acc + xon[1];
         hid = eluf(pre);
         prod = hid * fabsf(xon[0]);
         vt = fmaxf(xon[2], 0.0f) * v2w0;
-        const float pre_t = acc_t + xtg[1];
-        prod_t = eluf(pre_t) * fabsf(xtg[0]);
-        vt_t = fmaxf(xtg[2], 0.0f) * v2w1;
+        if constexpr (TARGET) {
+          const float pre_t = acc_t + xtg[1];
+          prod_t = eluf(pre_t) * fabsf(xtg[0]);
+          vt_t = fmaxf(xtg[2], 0.0f) * v2w1;
+        }
       }
       y = wave_sum(prod) + (wave_sum(vt) + v2b0);
-      yt = wave_sum(prod_t) + (wave_sum(vt_t) + v2b1);
+      if constexpr (TARGET) yt = wave_sum(prod_t) + (wave_sum(vt_t) + v2b1);
     }
     if (!valid) y = yt = 0.0f;
-    const float target = rew + gamma * (1.0f - term) * yt;   // q_learner.py:86
+    float target = rew + gamma * (1.0f - term) * yt;   // q_learner.py:86
+    if constexpr (!TARGET) target = valid ? G[m] : 0.0f;
     const float td = y - target;
     const float mtd = td * mask;
     l2 = td_loss(mtd, d.huber); msk = mask; abs_ = fabsf(mtd); qs = y * mask; tg = target * mask;
@@ -453,7 +534,8 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
       y = chosen;
       yt = tmax;
     }
-    const float target = rew + gamma * (1.0f - term) * yt;
+    float target = rew + gamma * (1.0f - term) * yt;
+    if constexpr (!TARGET) target = lambda_target(G, d.mixer, valid, m, n, lane);
     const float td = y - target;
     const float mtd = td * mask;
     const float dy = td_dy(mtd, mask, d.huber);
@@ -478,10 +560,13 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
   v2_slot[lane] = dv2;
 }
 
-template <int MA, int MN>
+template <int MA, int MN, int MODE = MIX_ONE_STEP, typename... LAM>
 __global__ __launch_bounds__(256) void mix_fast_kernel(Dims d, Rep rp, const float* __restrict__ P0,
                                                        const float* __restrict__ P1, Lay L, Work w,
-                                                       int32_t* curmax_out) {
+                                                       int32_t* curmax_out, LAM... lam) {
+  float* YT = nullptr;
+  const float* G = nullptr;
+  if constexpr (MODE != MIX_ONE_STEP) lambda_args(YT, G, lam...);
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + wv;
   const int E = d.E, NH = d.NH;
@@ -491,7 +576,8 @@ __global__ __launch_bounds__(256) void mix_fast_kernel(Dims d, Rep rp, const flo
   __shared__ float v2red[4][65];
   const float* hon = w.HYP + (int64_t)m * NH;
   const float* htg = w.HYP + ((int64_t)d.M + m) * NH;
-  mix_fast_row<MA, MN>(d, rp, P0, P1, L, w, curmax_out, m, lane, hon, htg, sc[wv], red[wv], v2red[wv]);
+  mix_fast_row<MA, MN, MODE>(d, rp, P0, P1, L, w, curmax_out, m, lane, hon, htg, sc[wv], red[wv], v2red[wv], YT, G);
+  if constexpr (MODE == MIX_LAMBDA_TARGETS) return;   // no loss terms in this pass
   __syncthreads();
   if (threadIdx.x < 8) {
     const int c = threadIdx.x;

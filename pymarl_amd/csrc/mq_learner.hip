@@ -7,6 +7,7 @@
 //   fc2      gemm  Q = W2 H + b2                                          both nets
 //   hyper    gemm  QMIX hypernet outputs of state[:, :-1] / state[:, 1:] both nets (QMIX only)
 //   mix      per (t, episode): chosen gather, double-Q select, mixer fwd, TD, masked L2 sums, mixer bwd
+//            (TD(lambda) targets, mq_config.td_lambda > 0: three launches, td_lambda_kernel.hpp)
 //   gru_bwd  recur BPTT; dW_hh, dW_ih, dW2 and biases accumulated in-kernel, dGI written out
 //   dx1      gemm  dP1 = (dGI W_ih) * [X1 > 0]
 //   dw1      gemm  [dW1 | db1] = dP1^T xin                                split-K
@@ -30,6 +31,7 @@
 #include "gru_bwd_fused.hpp"
 #include "gru_tiles.hpp"
 #include "mix_kernels.hpp"
+#include "td_lambda_kernel.hpp"
 #include "hyper_kernel.hpp"
 #include "dwh_kernel.hpp"
 #include "optim_kernels.hpp"
@@ -97,6 +99,7 @@ int lds_fits(const void* fn, size_t dyn, const char* what) {
   } while (0)
 
 constexpr int kNsplitMax = 128;
+constexpr size_t kLambdaLdsMax = 64 * 1024;   // dynamic LDS of td_lambda_kernel (checked in mq_create)
 enum Phase { PH_FC1, PH_GI, PH_GRUF, PH_FC2, PH_HYP, PH_MIX, PH_GRUB, PH_DX1, PH_DW1, PH_DWH, PH_RED, PH_APPLY,
              PH_N };
 const char* kPhaseNames = "fc1;gi;gru_fwd;fc2;hyper;mix;gru_bwd;dx1;dw1;dwh;reduce;apply";
@@ -161,6 +164,13 @@ struct mq_handle {
   bool pair_hyp_epi = plan_flag("pair_hyp_epi");   // the pair forward's hypernet as its epilogue, not on waves 4 / 5
   // mix_kernel<false> where mix_kernel<true> (staged selection rows) would run
   bool mix_generic = plan_flag("mix_generic");
+  // the TD(lambda) passes of the mixer tail (td_lambda_kernel.hpp) even at cfg.td_lambda = 0, where they compute the
+  // one-step target through the scan (A/B runs and tests)
+  bool lambda_path = plan_int("lambda_path", 0) != 0;
+  // their workspace, allocated only for a handle that runs them: y' and the lambda targets, [max_seq * max_batch]
+  // (no mixer: x n_agents) floats each
+  float *YT = nullptr, *G = nullptr;
+  bool have_lambda = false;   // the last step ran them (mq_copy_intermediate 4 / 5)
   int num_cu = 0;
   // timing: a ring of `slots` steps x PH_N (start, stop) event pairs; phases outside `mask` are not recorded
   int slots = 0;
@@ -292,6 +302,40 @@ hipError_t launch_gru_bwd(const Dims& d, const Rep& rp, const mq_handle* h, cons
   return hipGetLastError();
 }
 
+// The mixer tail's kernel for plan `mix` (MQ_MIX_*) in pass MODE (mix_kernels.hpp: the one-step tail, or one of the two
+// TD(lambda) passes around td_lambda_kernel).
+template <int MODE>
+void launch_mix(int mix, const mq_handle* h, const Dims& d, const Rep& rp, const Lay& L, const Work& w,
+                int32_t* curmax, hipStream_t s) {
+  const dim3 grid(h->nblk_mix), block(256);
+  const float *P0 = h->on, *P1 = h->tg;
+  if constexpr (MODE == MIX_ONE_STEP) {
+    if (mix == MQ_MIX_FAST16)
+      hipLaunchKernelGGL((mix_fast_kernel<16, 16>), grid, block, 0, s, d, rp, P0, P1, L, w, curmax);
+    else if (mix == MQ_MIX_FAST32)
+      hipLaunchKernelGGL((mix_fast_kernel<32, 16>), grid, block, 0, s, d, rp, P0, P1, L, w, curmax);
+    else if (mix == MQ_MIX_STREAM)
+      hipLaunchKernelGGL(mix_kernel<true>, grid, block, 0, s, d, rp, P0, P1, L, w, curmax);
+    else
+      hipLaunchKernelGGL(mix_kernel<false>, grid, block, 0, s, d, rp, P0, P1, L, w, curmax);
+  } else {   // the lambda passes: y' out (YT) or the targets in (G) as two trailing arguments
+    float* YT = h->YT;
+    const float* G = h->G;
+    if (mix == MQ_MIX_FAST16)
+      hipLaunchKernelGGL((mix_fast_kernel<16, 16, MODE, float*, const float*>), grid, block, 0, s, d, rp, P0, P1, L,
+                         w, curmax, YT, G);
+    else if (mix == MQ_MIX_FAST32)
+      hipLaunchKernelGGL((mix_fast_kernel<32, 16, MODE, float*, const float*>), grid, block, 0, s, d, rp, P0, P1, L,
+                         w, curmax, YT, G);
+    else if (mix == MQ_MIX_STREAM)
+      hipLaunchKernelGGL((mix_kernel<true, MODE, float*, const float*>), grid, block, 0, s, d, rp, P0, P1, L, w,
+                         curmax, YT, G);
+    else
+      hipLaunchKernelGGL((mix_kernel<false, MODE, float*, const float*>), grid, block, 0, s, d, rp, P0, P1, L, w,
+                         curmax, YT, G);
+  }
+}
+
 // Plan the slab reductions of one step: regions in gradient order, then the loss sums (not part of the norm).
 struct RedBuilder {
   RedPlan pl{};
@@ -371,6 +415,14 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
     return set_err(MQ_ERR_ARG, "mixing_embed_dim must be in [1, 64]");
   if (c.max_batch < 1 || c.max_seq < 2) return set_err(MQ_ERR_ARG, "max_batch >= 1 and max_seq >= 2 required");
   if (!(c.huber_delta >= 0.0f)) return set_err(MQ_ERR_ARG, "huber_delta must be >= 0 (0: the reference's L2 loss)");
+  if (!(c.td_lambda >= 0.0f && c.td_lambda <= 1.0f))
+    return set_err(MQ_ERR_ARG, "td_lambda must be in [0, 1] (0: the reference's one-step target)");
+  // the scan stages an episode's inputs in dynamic LDS (td_lambda_kernel.hpp): kept within what a launch may ask for
+  // without raising the kernel's dynamic-LDS attribute
+  if ((c.td_lambda > 0.0f || plan_int("lambda_path", 0) != 0) &&
+      td_lambda_lds_bytes(c.max_seq - 1, c.mixer == MQ_MIXER_NONE ? c.n_agents : 1) > kLambdaLdsMax)
+    return set_err(MQ_ERR_ARG, "td_lambda: max_seq " + std::to_string(c.max_seq) + " needs more than " +
+                                   std::to_string(kLambdaLdsMax) + " B of LDS for the TD(lambda) scan");
 
   mq_handle* h = new mq_handle();
   h->cfg = c;
@@ -433,6 +485,16 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
   w.XIN = base + offs[18];
   w.S0 = base + offs[19];
   w.curmax = h->curmax_ws;
+  if (c.td_lambda > 0.0f || h->lambda_path) {
+    const int64_t len = align_up((int64_t)c.max_seq * c.max_batch * (c.mixer == MQ_MIXER_NONE ? n : 1));
+    e = hipMalloc((void**)&h->YT, 2 * len * sizeof(float));
+    if (e != hipSuccess) {
+      (void)hipFree(h->ws);
+      delete h;
+      return set_err(MQ_ERR_HIP, std::string("TD(lambda) workspace hipMalloc: ") + hipGetErrorString(e));
+    }
+    h->G = h->YT + len;
+  }
   *out = h;
   return MQ_OK;
 }
@@ -445,6 +507,7 @@ int mq_destroy(mq_handle* h) {
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->ws) (void)hipFree(h->ws);
+  if (h->YT) (void)hipFree(h->YT);
   if (h->comm && h->comm_owned) (void)ncclCommDestroy(h->comm);
   delete h;
   return MQ_OK;
@@ -611,19 +674,25 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
     const bool stream = mix_stream_ok(d.n, d.A) && !h->mix_generic;
     plan.mix = fast && d.A <= 16 ? MQ_MIX_FAST16 : fast && d.A <= 32 ? MQ_MIX_FAST32 : stream ? MQ_MIX_STREAM
                                                                                              : MQ_MIX_GENERIC;
-    if (fast && d.A <= 16)
-      hipLaunchKernelGGL((mix_fast_kernel<16, 16>), dim3(h->nblk_mix), dim3(256), 0, s, d, rp, (const float*)h->on,
-                         (const float*)h->tg, L, w, curmax);
-    else if (fast && d.A <= 32)
-      hipLaunchKernelGGL((mix_fast_kernel<32, 16>), dim3(h->nblk_mix), dim3(256), 0, s, d, rp, (const float*)h->on,
-                         (const float*)h->tg, L, w, curmax);
-    else if (stream)
-      hipLaunchKernelGGL(mix_kernel<true>, dim3(h->nblk_mix), dim3(256), 0, s, d, rp, (const float*)h->on,
-                         (const float*)h->tg, L, w, curmax);
-    else
-      hipLaunchKernelGGL(mix_kernel<false>, dim3(h->nblk_mix), dim3(256), 0, s, d, rp, (const float*)h->on,
-                         (const float*)h->tg, L, w, curmax);
-    MQ_HIP(hipGetLastError());
+    const bool lambda = h->YT != nullptr;   // cfg.td_lambda > 0 or MQ_PLAN lambda_path=1 (mq_create)
+    plan.td_lambda = lambda ? 1 : 0;
+    if (!lambda) {
+      launch_mix<MIX_ONE_STEP>(plan.mix, h, d, rp, L, w, curmax, s);
+      MQ_HIP(hipGetLastError());
+    } else {
+      // TD(lambda): y' of every (t, b), the backward scan over t per episode, then the loss against its targets
+      const int k = c.mixer == MQ_MIXER_NONE ? d.n : 1;
+      const size_t dyn = td_lambda_lds_bytes(d.T, k);
+      MQ_LDS(td_lambda_kernel, dyn);
+      launch_mix<MIX_LAMBDA_TARGETS>(plan.mix, h, d, rp, L, w, curmax, s);
+      MQ_HIP(hipGetLastError());
+      const float lg = (float)((double)c.td_lambda * (double)c.gamma);
+      const float og = (float)((1.0 - (double)c.td_lambda) * (double)c.gamma);
+      hipLaunchKernelGGL(td_lambda_kernel, dim3(d.B), dim3(256), dyn, s, d, rp, (const float*)h->YT, h->G, k, lg, og);
+      MQ_HIP(hipGetLastError());
+      launch_mix<MIX_LAMBDA_LOSS>(plan.mix, h, d, rp, L, w, curmax, s);
+      MQ_HIP(hipGetLastError());
+    }
   }
   pt.begin(PH_GRUB);
   bool dwh_in_bwd = false;
@@ -774,6 +843,7 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
   h->last = d;
   h->plan = plan;
   h->have_fb = true;
+  h->have_lambda = plan.td_lambda != 0;
   return MQ_OK;
 }
 
@@ -896,6 +966,12 @@ int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, vo
     case 1: src = h->w.Q + RT * d.A; cnt = RT * d.A; break;
     case 2: src = h->w.dch; cnt = (int64_t)d.T * d.R; break;
     case 3: src = h->w.X1; cnt = RT * mq::H; break;
+    case 4:
+    case 5:
+      if (!h->have_lambda) return set_err(MQ_ERR_STATE, "the last step did not run the TD(lambda) passes");
+      src = which == 4 ? h->YT : h->G;
+      cnt = (int64_t)d.T * d.B * (d.mixer == MQ_MIXER_NONE ? d.n : 1);
+      break;
     default: return set_err(MQ_ERR_ARG, "unknown intermediate id");
   }
   if (count) *count = cnt;

@@ -34,6 +34,7 @@ from ..modules.mixers.qmix import QMixer
 from ..modules.mixers.vdn import VDNMixer
 
 MIXER_IDS = {None: _lib.MIXER_NONE, "vdn": _lib.MIXER_VDN, "qmix": _lib.MIXER_QMIX}
+Q_TARGETS = ("one_step", "td_lambda")
 _FIELDS = [("obs", th.float32), ("state", th.float32), ("actions", th.int64), ("avail_actions", th.int32),
            ("reward", th.float32), ("terminated", th.uint8), ("filled", th.int64)]
 
@@ -64,6 +65,13 @@ def make_config(args, mixer, input_dim=None, max_batch=1, max_seq=2):
     # opt-in masked Huber TD loss (north_star; the reference has L2 only, q_learner.py:96-97): td_loss: huber,
     # huber_delta (default 1.0); anything else keeps L2
     cfg.huber_delta = float(getattr(args, "huber_delta", 1.0)) if getattr(args, "td_loss", "l2") == "huber" else 0.0
+    # opt-in TD(lambda) targets (the reference's Q learner has the one-step target only, q_learner.py:86; the
+    # function is its rl_utils.build_td_lambda_targets): q_targets: td_lambda selects them with args.td_lambda.
+    # Without it args.td_lambda is ignored: COMA-style configs carry td_lambda: 0.8 globally
+    q_targets = getattr(args, "q_targets", "one_step")
+    if q_targets not in Q_TARGETS:
+        raise ValueError("q_targets {} not recognised (one of {}).".format(q_targets, ", ".join(Q_TARGETS)))
+    cfg.td_lambda = float(args.td_lambda) if q_targets == "td_lambda" else 0.0
     return cfg
 
 
@@ -354,7 +362,8 @@ class QLearner:
 
     def last_plan(self):
         """Kernel variants the last train() launched (mq_last_plan): rows, fused_fwd, rw_fwd, fused_bwd, rw_bwd,
-        inline_ids, hyper, mix, tiles, dwh (where QMIX's dW_hyper ran: "red1" or "bptt_grid")."""
+        inline_ids, hyper, mix, tiles, dwh (where QMIX's dW_hyper ran: "red1" or "bptt_grid"), td_lambda (1: the
+        mixer tail ran as the TD(lambda) passes)."""
         pl = _lib.MQPlan()
         _lib.check(self._handle.lib.mq_last_plan(self._handle.h, ctypes.byref(pl)))
         d = pl.as_dict()
@@ -372,7 +381,9 @@ class QLearner:
 
     def last_intermediate(self, which):
         """0 / 1: online / target mac_out as (B, T+1, n, A); 2: dLoss_num/dchosen as (B, T, n);
-        3: online relu(fc1(inputs)) as (B, T+1, n, 64)."""
+        3: online relu(fc1(inputs)) as (B, T+1, n, 64). After a TD(lambda) step (last_plan()["td_lambda"] == 1):
+        4: y', the target network's mixed value at step t + 1, as (B, T, 1), or (B, T, n) without a mixer;
+        5: the lambda targets in the same shape."""
         B, Tp = self._last_batch
         n, A = self.args.n_agents, self.args.n_actions
         cnt = ctypes.c_int64()
@@ -384,6 +395,8 @@ class QLearner:
             return out.view(Tp, B, n, A).permute(1, 0, 2, 3)
         if which == 3:
             return out.view(Tp, B, n, -1).permute(1, 0, 2, 3)
+        if which in (4, 5):
+            return out.view(Tp - 1, B, -1).permute(1, 0, 2)
         return out.view(Tp - 1, B, n).permute(1, 0, 2)
 
     def set_timing(self, slots=1, phases=None):
