@@ -177,6 +177,9 @@ typedef struct mq_plan {
   int32_t td_lambda;     /* 1: the mixer tail ran as the TD(lambda) passes (mq_config.td_lambda > 0, or MQ_PLAN
                             lambda_path=1, which runs them at td_lambda = 0 too: the one-step target through the scan,
                             for A/B runs and tests); `mix` names the variant of both mixer passes */
+  int32_t bwd_lean;      /* 1: the fused BPTT ran its lean per-step path (walked chain addresses, per-chunk fc2-gradient
+                            inputs, dW2 / db2 in registers): the default behind the row-pair forward (fused_fwd = 2,
+                            fused_bwd = 1); MQ_PLAN bwd_lean=0 keeps the classic step (bitwise the same results) */
 } mq_plan;
 int mq_last_plan(const mq_handle* h, mq_plan* out);
 

@@ -21,6 +21,7 @@
 // MFMA maps as gru_fwd_fused.hpp (v_mfma_f32_16x16x4_f32: A[i = c][kk = g], B[kk = g][j = c], D[4g + r][c]).
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 #include "gru_fwd_fused.hpp"
 #include "dwh_kernel.hpp"
 
@@ -70,8 +71,26 @@ inline bool fused_bwd_ok(int I, int O, int A, int n, int64_t RT) { return fused_
 // bias slabs written; producer wave 4 in the tail: [6] dW_hh of chunk 0 done, [7] its slab stores issued, [8] past the
 // tail's first barrier, [9] dW_ih done, [10] its slab issued, [11] dX1 done; [16 + u] chain wave 0's step t = Tp - 1 - u
 // done.
+//
+// LEAN (MQ_PLAN bwd_lean, default on; 0 is the path above, bitwise the same results): work whose inputs are known long
+// before dh leaves the per-step path.
+//  * LEAN_ADDR: the chain's loads of steps Tp - 4 .. 1 (every load of the 4-step loop but its last round) take a
+//    wave-uniform gate-record base and a per-lane aux pointer, each stepped down by a constant, instead of forming
+//    both addresses from t with 64-bit multiplies; the rounds at the edges (the three loads of the prologue, where dch
+//    row T is clamped, and the last steps, where h row -1 is) keep the clamped form.
+//  * LEAN_FC2: the producers load dchosen and the action of a chunk's 16 steps one chunk ahead into one register
+//    (lanes 0-15 / 16-31) and read them per step with v_readlane; lane (k, q) keeps dW2[a][k] and db2[a] of its
+//    actions a = q, q + 4, q + 8, q + 12 in registers (a 0 / dchosen factor per slot, same t order: bitwise the LDS
+//    read-modify-writes of the path above) and stores them once in the tail. No global load is waited for and no
+//    exec-masked branch is taken inside a step.
+//  * LEAN_COEF (needs w.rec_coef: the row-pair forward wrote the coefficient record, learner_types.hpp gru_coef):
+//    lane q loads plane q of (a_r, a_z, a_n, a_n r) and lane 1's aux load is z instead of a second dchosen, so the
+//    per-step coefficient work shrinks to the z / dchosen / action / h_{t-1} broadcasts, dgh_n's coefficient for
+//    lane 2 from lane 3, and wd = dchosen W2[a]. Every other forward keeps the gate record and the in-chain form.
+constexpr int LEAN_ADDR = 1, LEAN_FC2 = 2, LEAN_COEF = 4;
+constexpr int kBwdLean = LEAN_ADDR | LEAN_FC2 | LEAN_COEF;
 constexpr int BSTH = 16, BSTN = BSTH + 152;
-template <int DWH = 0, bool STAMP = false>
+template <int DWH = 0, bool STAMP = false, int LEAN = 0>
 __global__ __launch_bounds__(512) void gru_bwd_fused_kernel(Dims d, Rep rp, const float* __restrict__ P, Lay L,
                                                             Work w, int64_t slab_len, int64_t slab1_len) {
   __shared__ BwdFusedLds S;
@@ -172,16 +191,30 @@ __global__ __launch_bounds__(512) void gru_bwd_fused_kernel(Dims d, Rep rp, cons
     struct In { float g, aux, w2, wd, ci, ch, hq, gz; };   // wd .. gz: the step's coefficients
     const float* aux_base;
     int64_t aux_stride;
+    constexpr bool COEF = (LEAN & LEAN_COEF) != 0;
+    constexpr int GP = COEF ? 5 * H : 4 * H;   // the record's row pitch: four gate planes, or five coefficient planes
     if (q == 0) { aux_base = w.Hs + (int64_t)r * H + k - (int64_t)R * H; aux_stride = (int64_t)R * H; }
     else if (q == 3) { aux_base = (const float*)arow; aux_stride = 2 * (int64_t)d.n; }
+    else if (COEF && q == 1) { aux_base = w.Gates + (int64_t)r * GP + 4 * H + k; aux_stride = (int64_t)R * GP; }
     else { aux_base = w.dch + r; aux_stride = R; }
-    const float* g_base = w.Gates + (int64_t)r * (4 * H) + q * H + k;
-    const int e0 = q == 0 ? 1 : 0, e12 = (q == 1 || q == 2) ? 1 : 0;
+    const float* g_base = w.Gates + (int64_t)r * GP + q * H + k;
+    const int e0 = q == 0 ? 1 : 0, e12 = ((q == 1 && !COEF) || q == 2) ? 1 : 0;
     auto load = [&](int t, In& s) {
       const int tc = max(t, 0);
       const int idx = tc + (e0 & (tc == 0 ? 1 : 0)) - (e12 & (tc >= T ? 1 : 0));
-      s.g = g_base[(int64_t)tc * R * (4 * H)];
+      s.g = g_base[(int64_t)tc * R * GP];
       s.aux = aux_base[idx * aux_stride];
+    };
+    // LEAN_ADDR: the loop's loads walk down from step Tp - 4
+    const float* g_walk = w.Gates + (int64_t)(Tp - 4) * R * GP;   // wave-uniform
+    const uint32_t g_lane = (uint32_t)r * GP + q * H + k;
+    const char* aux_walk = (const char*)(aux_base + (int64_t)(Tp - 4) * aux_stride);
+    const uint32_t aux_step = (uint32_t)aux_stride * 4;   // bytes; (R H, R or 2 n) * 4 < 2^32
+    auto load_walk = [&](In& s) {   // steps 1 .. T - 1 only: no edge clamp applies
+      s.g = ld_u32(g_walk, g_lane);
+      s.aux = *(const float*)aux_walk;
+      g_walk -= (int64_t)R * GP;
+      aux_walk -= aux_step;
     };
     auto lookup_w2 = [&](In& s) { s.w2 = w2_s[__builtin_bit_cast(int, quad_bcast<3>(s.aux)) * H + k]; };
     // lane-split selectors as 0/1 factors (multiply-add selects, no branches)
@@ -189,22 +222,30 @@ __global__ __launch_bounds__(512) void gru_bwd_fused_kernel(Dims d, Rep rp, cons
     const float m3 = q == 3 ? 1.0f : 0.0f;
     float carry = 0.0f, db_i = 0.0f, db_h = 0.0f;   // bias grads: this lane's component q of b_ih / b_hh
     // the step's coefficients (see the note above), computed one step ahead
-    auto coeffs = [&](int t, In& s) {
-      const float gr = quad_bcast<0>(s.g), gz = quad_bcast<1>(s.g), gn = quad_bcast<2>(s.g), ghn = quad_bcast<3>(s.g);
+    // (fuse: gru_coef's form of 1 - n^2 for step t, a constant of the step copy that agrees with coef_fused(t, Tp))
+    auto coeffs = [&](auto fuse, int t, In& s) {
       const float hp = t > 0 ? quad_bcast<0>(s.aux) : 0.0f;
       const float dchv = t < T ? quad_bcast<2>(s.aux) : 0.0f;
-      const float an = (1.0f - gz) * (1.0f - gn * gn);
-      const float ar = (an * ghn) * (gr * (1.0f - gr));
-      const float az = (hp - gn) * (gz * (1.0f - gz));
-      const float rzc = fmaf(m0, ar, m1 * az);
-      s.ci = fmaf(m2 + m3, an, rzc);       // dgi component q (q = 3: the unused slot)
-      s.ch = fmaf(m2, an * gr, rzc);       // dgh component q (q = 3: 0, the slot holds h_{t-1})
+      if constexpr (COEF) {
+        // s.g is this lane's coefficient already: a_r, a_z, a_n; lane 3 holds a_n r, which is lane 2's dgh factor
+        s.ci = s.g;                                            // (q = 3: the unused slot)
+        s.ch = fmaf(m2, quad_bcast<3>(s.g), (m0 + m1) * s.g);   // (q = 3: 0, the slot holds h_{t-1})
+        s.gz = quad_bcast<1>(s.aux);
+      } else {
+        const float gr = quad_bcast<0>(s.g), gz = quad_bcast<1>(s.g), gn = quad_bcast<2>(s.g);
+        const float ghn = quad_bcast<3>(s.g);
+        const GruCoef c = gru_coef(gr, gz, gn, ghn, hp, decltype(fuse)::value);
+        const float rzc = fmaf(m0, c.ar, m1 * c.az);
+        s.ci = fmaf(m2 + m3, c.an, rzc);    // dgi component q (q = 3: the unused slot)
+        s.ch = fmaf(m2, c.anr, rzc);        // dgh component q (q = 3: 0, the slot holds h_{t-1})
+        s.gz = gz;
+      }
       s.hq = m3 * hp;
       s.wd = dchv * s.w2;
-      s.gz = gz;
     };
-    auto lstep = [&](int t, const In& cur, In& nxt, In& ahead) {
-      load(t - 3, ahead);
+    auto lstep = [&](auto walk, auto fuse, int t, const In& cur, In& nxt, In& ahead) {
+      if constexpr (decltype(walk)::value) load_walk(ahead);
+      else load(t - 3, ahead);
       const int p = t & (FCH - 1), cb = (t / FCH) & 1;
       const float dh = carry + cur.wd;
       const float mine_i = dh * cur.ci;
@@ -218,7 +259,7 @@ __global__ __launch_bounds__(512) void gru_bwd_fused_kernel(Dims d, Rep rp, cons
       const f32x4* d12 = (const f32x4*)(&S.gh[cb][p][12 * c16]);
       const f32x4 dv[3] = {d12[0], d12[1], d12[2]};
       lookup_w2(nxt);   // the next step's W2[a][k] and coefficients, beside this step's LDS reads and FMAs
-      coeffs(t - 1, nxt);
+      coeffs(fuse, t - 1, nxt);
       carry = fmaf(dh, cur.gz, k12_sum(dv));
       if constexpr (STAMP) { if (tid < 64 && Tp - 1 - t < BSTN - BSTH) bstamp(BSTH + Tp - 1 - t); }
     };
@@ -244,17 +285,30 @@ __global__ __launch_bounds__(512) void gru_bwd_fused_kernel(Dims d, Rep rp, cons
     lds_barrier();
     if (tid == 0) bstamp(1);
     lookup_w2(sa);
-    coeffs(Tp - 1, sa);
+    coeffs(std::true_type{}, Tp - 1, sa);
     int t = Tp - 1;
-    for (; t - 3 >= 0; t -= 4) {
-      lstep(t, sa, sb, sd);
-      lstep(t - 1, sb, sc, sa);
-      lstep(t - 2, sc, sd, sb);
-      lstep(t - 3, sd, sa, sc);
+    constexpr std::false_type by_t{};
+    // a round's third step prepares the coefficients of t - 3 = Tp - 4, Tp - 8, ..: the unfused form (gru_coef)
+    constexpr std::true_type fu{};
+    constexpr std::false_type unf{};
+    if constexpr ((LEAN & LEAN_ADDR) != 0) {
+      constexpr std::true_type walk{};
+      for (; t - 6 >= 1; t -= 4) {   // this round loads steps t - 3 .. t - 6, all inside 1 .. T - 1
+        lstep(walk, fu, t, sa, sb, sd);
+        lstep(walk, fu, t - 1, sb, sc, sa);
+        lstep(walk, unf, t - 2, sc, sd, sb);
+        lstep(walk, fu, t - 3, sd, sa, sc);
+      }
     }
-    if (t >= 0) lstep(t, sa, sb, sd);
-    if (t - 1 >= 0) lstep(t - 1, sb, sc, sa);
-    if (t - 2 >= 0) lstep(t - 2, sc, sd, sb);
+    for (; t - 3 >= 0; t -= 4) {
+      lstep(by_t, fu, t, sa, sb, sd);
+      lstep(by_t, fu, t - 1, sb, sc, sa);
+      lstep(by_t, unf, t - 2, sc, sd, sb);
+      lstep(by_t, fu, t - 3, sd, sa, sc);
+    }
+    if (t >= 0) lstep(by_t, fu, t, sa, sb, sd);
+    if (t - 1 >= 0) lstep(by_t, fu, t - 1, sb, sc, sa);
+    if (t - 2 >= 0) lstep(by_t, fu, t - 2, sc, sd, sb);
     if (tid == 0) bstamp(2);
     lds_barrier();   // producer tail: chunk 0 (2 barriers)
     lds_barrier();
@@ -380,7 +434,35 @@ __global__ __launch_bounds__(512) void gru_bwd_fused_kernel(Dims d, Rep rp, cons
       }
       h_next = S.gh[cb][p][3 * H + k];
     };
-    fc2_fetch(Tp - 1);
+    // LEAN_FC2: a chunk's 16 (dchosen, action) pairs in one register, the sums of this lane's four actions in pairs
+    // {dW2[a][k], db2[a]}
+    float fin_c = 0.0f, fin_n = 0.0f;
+    f32x2 acc2[4] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
+    auto issue_fc2 = [&](int C, float& fin) {
+      const int tt = FCH * C + (lane & 15);
+      const float* src = (lane & 16) ? (const float*)(arow + (int64_t)min(tt, Tp - 1) * d.n)
+                                     : w.dch + (int64_t)max(min(tt, T - 1), 0) * R + r;
+      fin = *src;
+    };
+    auto fc2_lean = [&](int t, int p) {   // p = t % 16, a constant of the unrolled step
+      const int cb = (t / FCH) & 1;
+      const float dchv = t < T ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, fin_c), p))
+                               : 0.0f;
+      const int amq = __builtin_amdgcn_readlane(__builtin_bit_cast(int, fin_c), 16 + p) - q;
+      const f32x2 h1 = {h_next, 1.0f};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float m = amq == 4 * j ? dchv : 0.0f;
+        acc2[j] = pk_fma(f32x2{m, m}, h1, acc2[j]);
+      }
+      h_next = S.gh[cb][p][3 * H + k];
+    };
+    if constexpr ((LEAN & LEAN_FC2) != 0) {
+      issue_fc2(cl, fin_c);
+      if (cl >= 1) issue_fc2(cl - 1, fin_n);
+    } else {
+      fc2_fetch(Tp - 1);
+    }
     issue_rows(cl);   // the X1 / XIN rows one chunk ahead (the top chunk's up front)
     stage_common();
 
@@ -388,12 +470,14 @@ __global__ __launch_bounds__(512) void gru_bwd_fused_kernel(Dims d, Rep rp, cons
     for (int c = cl; c >= 0; --c) {
       const int C = c + 1;
       const bool work = C <= cl;
+      if constexpr ((LEAN & LEAN_FC2) != 0) { if (c < cl) fin_c = fin_n; }
 #pragma unroll
       for (int u = 0; u < FCH; ++u) {
         const int t = FCH * c + FCH - 1 - u;
         if (t >= Tp) continue;
         lds_barrier();   // step t's records published
-        fc2_grads(t);
+        if constexpr ((LEAN & LEAN_FC2) != 0) fc2_lean(t, FCH - 1 - u);
+        else fc2_grads(t);
         if (work) {
           if (u >= 1 && u <= 4) dw_rec(C, u - 1, u, false);
           if (u == 4) store_rows(C);
@@ -404,6 +488,7 @@ __global__ __launch_bounds__(512) void gru_bwd_fused_kernel(Dims d, Rep rp, cons
           if (u == 14) dw1_part(1, 2);
           if (u == 15) dw1_part(2, 4);
         }
+        if constexpr ((LEAN & LEAN_FC2) != 0) { if (u == 5 && c < cl && c >= 1) issue_fc2(c - 1, fin_n); }
         if (u == 5 && c < cl) issue_rows(c);   // stored at u = 4 of the next chunk
       }
     }
@@ -447,6 +532,16 @@ __global__ __launch_bounds__(512) void gru_bwd_fused_kernel(Dims d, Rep rp, cons
         if (nn < I) slab1[m * I + nn] = acc_w1[nt][e];
       }
     S.db1[g][16 * wv + c16] = db1p;
+    if constexpr ((LEAN & LEAN_FC2) != 0) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int a = 4 * j + q;
+        if (a < A) {
+          dw2_s[a * H + k] = acc2[j].x;
+          if (k == 0) db2_s[a] = acc2[j].y;
+        }
+      }
+    }
   }
   lds_barrier();
   if (tid == 0) bstamp(4);
@@ -466,17 +561,25 @@ __global__ __launch_bounds__(512) void gru_bwd_fused_kernel(Dims d, Rep rp, cons
 }
 
 // Host: the fused BPTT, with dW_hyper's tiles appended (DWH = 1; w.dwh_* set by the caller) or without.
+#define MQ_BWD_FUSED_LAUNCH(DW, ST, LN) \
+  hipLaunchKernelGGL((gru_bwd_fused_kernel<DW, ST, LN>), grid, dim3(512), dyn, s, d, rp, P, L, w, slab_len, slab1_len)
 inline void launch_bwd_fused_dwh(size_t dyn, hipStream_t s, const Dims& d, const Rep& rp, const float* P,
-                                 const Lay& L, const Work& w, int64_t slab_len, int64_t slab1_len) {
+                                 const Lay& L, const Work& w, int64_t slab_len, int64_t slab1_len, bool lean) {
   const dim3 grid(d.R + (w.dwh_n + 1) / 2);
-  hipLaunchKernelGGL((gru_bwd_fused_kernel<1>), grid, dim3(512), dyn, s, d, rp, P, L, w, slab_len, slab1_len);
+  if (lean) MQ_BWD_FUSED_LAUNCH(1, false, kBwdLean);
+  else MQ_BWD_FUSED_LAUNCH(1, false, 0);
 }
 inline void launch_bwd_fused(dim3 grid, size_t dyn, hipStream_t s, const Dims& d, const Rep& rp, const float* P,
-                             const Lay& L, const Work& w, int64_t slab_len, int64_t slab1_len, bool stamp = false) {
-  if (stamp)
-    hipLaunchKernelGGL((gru_bwd_fused_kernel<0, true>), grid, dim3(512), dyn, s, d, rp, P, L, w, slab_len, slab1_len);
-  else
-    hipLaunchKernelGGL((gru_bwd_fused_kernel<0>), grid, dim3(512), dyn, s, d, rp, P, L, w, slab_len, slab1_len);
+                             const Lay& L, const Work& w, int64_t slab_len, int64_t slab1_len, bool lean,
+                             bool stamp = false) {
+  if (stamp) {
+    if (lean) MQ_BWD_FUSED_LAUNCH(0, true, kBwdLean);
+    else MQ_BWD_FUSED_LAUNCH(0, true, 0);
+  } else {
+    if (lean) MQ_BWD_FUSED_LAUNCH(0, false, kBwdLean);
+    else MQ_BWD_FUSED_LAUNCH(0, false, 0);
+  }
 }
+#undef MQ_BWD_FUSED_LAUNCH
 
 }  // namespace mq

@@ -507,6 +507,30 @@ MQ_DEV void pair_body(const Dims& d, const Rep& rp, const float* __restrict__ P0
   // 16 steps x 64 units; thread (step 4 k + (ptid >> 6), unit ptid & 63), coalesced along the units
   auto store_records = [&](int cc) {
     const int t0 = FCH * cc, j = ptid & 63;
+    if (w.rec_coef) {
+      // the record holds what the fused BPTT's chain consumes instead: five planes a_r, a_z, a_n, a_n r, z (gru_coef;
+      // row pitch 5 H), so the chain does not rebuild them from the gates every step. h_{t-1} of a chunk's first step
+      // is the previous chunk's last h, whose slot the recurrence is overwriting by now: it is kept in S.h0, which
+      // holds init_hidden's zeros for t = 0 and is free once chunk 0 is done (written and read by the same thread).
+      // One step at a time: the producers have no registers to spare for four steps' loads in flight.
+#pragma unroll 1
+      for (int k = 0; k < 4; ++k) {
+        const int i = 4 * k + (ptid >> 6), t = t0 + i;
+        const f32x4 gv = S.grec[cc & 1][i][j];
+        const float hv = S.hs[0][cc & 1][i][j];
+        const float hp = *(i > 0 ? &S.hs[0][cc & 1][i - 1][j] : &S.h0[j]);
+        const bool ok = t < Tp;
+        buf_st(buf_rsrc(w.Hs + (int64_t)min(t, Tp - 1) * RH), ok ? ((uint32_t)r * H + j) * 4 : kDrop, hv);
+        const GruCoef cf = gru_coef(gv[0], gv[1], gv[2], gv[3], hp, coef_fused(t, Tp));
+        const auto gb = buf_rsrc(w.Gates + (int64_t)min(t, Tp - 1) * (5 * RH));
+        const uint32_t go = ((uint32_t)r * (5 * H) + j) * 4;
+        const float pl[5] = {cf.ar, cf.az, cf.an, cf.anr, gv[1]};
+#pragma unroll
+        for (int q = 0; q < 5; ++q) buf_st(gb, ok ? go + q * 4 * H : kDrop, pl[q]);
+      }
+      if (ptid < H) S.h0[j] = S.hs[0][cc & 1][FCH - 1][j];
+      return;
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int i = 4 * k + (ptid >> 6), t = t0 + i;

@@ -58,7 +58,7 @@ struct Work {
   float* X1;      // [2][RT][H]   relu(fc1) per net
   float* GI;      // [2][RT][3H]  W_ih x1 + b_ih per net
   float* Hs;      // [2][RT][H]   hidden after step t per net
-  float* Gates;   // [RT][4H]     online r, z, n, W_hn h + b_hn
+  float* Gates;   // [RT][4H]     online r, z, n, W_hn h + b_hn; rec_coef: [RT][5H] a_r, a_z, a_n, a_n r, z (gru_coef)
   float* Q;       // [2][RT][A]   mac_out / target_mac_out
   float* HYP;     // [2][M][NH]   QMIX hypernet outputs per net (state t for online, t+1 for target)
   float* dHYP;    // [M][NH]
@@ -80,7 +80,30 @@ struct Work {
   // tile count
   int64_t dwh_len = 0;
   int dwh_ns = 0, dwh_tj = 0, dwh_n = 0;
+  // 1: the row-pair forward writes the BPTT's coefficient record instead of the gate record (the fused BPTT's lean
+  // path reads it; every other forward and BPTT keeps the gate record)
+  int rec_coef = 0;
 };
+
+// The linearised BPTT step's coefficients of one unit (gru_bwd_fused.hpp) from the forward's gate record (r, z, n,
+// ghn = W_hn h + b_hn) and h_{t-1}: d(a_r) = dh a_r, d(a_z) = dh a_z, d(a_n) = dh a_n, dgh_n = dh (a_n r).
+// Contraction is pinned, so the forward's producers and the BPTT's in-chain form yield the same bits. 1 - n^2 has two
+// forms, one fma (fuse_n2) or a rounded product and a subtraction: the in-chain form used to leave the choice to the
+// compiler, which fused it in every step copy of the chain but the third of each 4-step round, and results stay
+// bit-identical to those builds. coef_fused says which form step t of Tp takes (the rounds start at t = Tp - 1, so
+// the third steps' coefficients are those of t = Tp - 4, Tp - 8, ..).
+MQ_DEV bool coef_fused(int t, int Tp) { return t > Tp - 4 || ((Tp - t) & 3) != 0; }
+struct GruCoef { float ar, az, an, anr; };
+MQ_DEV GruCoef gru_coef(float gr, float gz, float gn, float ghn, float hp, bool fuse_n2) {
+#pragma clang fp contract(off)
+  GruCoef c;
+  const float n2 = gn * gn;
+  c.an = (1.0f - gz) * (fuse_n2 ? fmaf(-gn, gn, 1.0f) : 1.0f - n2);
+  c.ar = (c.an * ghn) * (gr * (1.0f - gr));
+  c.az = (hp - gn) * (gz * (1.0f - gz));
+  c.anr = c.an * gr;
+  return c;
+}
 
 MQ_DEV void split_tr(const Dims& d, uint32_t tr, int& t, int& r, int& b, int& ag) {
   t = (int)fdiv(tr, d.dR);

@@ -161,6 +161,9 @@ struct mq_handle {
   // the row-pair forward (gru_fwd_pair.hpp: both nets of a row in one workgroup, one per CU) when the rows fit one
   // wave of workgroups; fwd_pair=0 keeps the one-row-net kernel, =1 forces the pair
   int fwd_pair = plan_int("fwd_pair", -1);
+  // the fused BPTT's lean per-step path (gru_bwd_fused.hpp LEAN) behind the row-pair forward; bwd_lean=0 keeps the
+  // classic step (bitwise the same results)
+  int bwd_lean = plan_int("bwd_lean", -1);
   bool pair_hyp_epi = plan_flag("pair_hyp_epi");   // the pair forward's hypernet as its epilogue, not on waves 4 / 5
   // mix_kernel<false> where mix_kernel<true> (staged selection rows) would run
   bool mix_generic = plan_flag("mix_generic");
@@ -447,7 +450,7 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
       2 * RT * Hd,                                   // X1
       2 * RT * 3 * Hd,                               // GI
       2 * RT * Hd,                                   // Hs (both nets)
-      RT * 4 * Hd,                                   // Gates
+      RT * 5 * Hd,                                   // Gates (four gate planes, or five coefficient planes)
       2 * RT * A,                                    // Q
       2 * Mm * NH,                                   // HYP
       Mm * NH,                                       // dHYP
@@ -566,6 +569,7 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
                          !h->force_unfused_bwd;
   const int rw_fwd = pick_rw(d.R, 512);
   bool hyp_in_fwd = false;
+  bool pair_fwd = false;   // the row-pair forward runs (plan.fused_fwd = 2)
   plan.tiles = tiles ? 1 : 0;
   if (tiles) {
     // row tiles of 32 (two M-tiles) per workgroup, both nets: the recurrence and fc1 / W_ih / fc2 on MFMA
@@ -594,6 +598,7 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
       launch_fwd_fused_hyp(s, d, rp, (const float*)h->on, (const float*)h->tg, L, w);
     } else if (pair) {
       plan.fused_fwd = 2;
+      pair_fwd = true;
       // the QMIX hypernet as the pair kernel's epilogue (hyp_in_fwd=0 keeps hyper_ws_kernel after it)
       hyp_in_fwd = h->hyp_in_fwd != 0 && c.mixer == MQ_MIXER_QMIX && hyper_ws_ok(d.S, d.E, d.NH, d.M) &&
                    hyf_ok(d.S, d.E, d.NH, d.M);
@@ -606,6 +611,8 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
       const int pair_hyp = !hyp_in_fwd ? 0 : (2 * ((d.M + 31) / 32) <= d.R && !h->pair_hyp_epi) ? 2 : 1;
       // the stamp build has the 5-slot gather only: shapes past it run unstamped (never a partial gather)
       const bool stamp = want_stamp && d.Tp <= 512 && FCH * d.O <= 256 * 5;
+      // the fused BPTT's lean path reads the coefficient record (gru_bwd_fused.hpp LEAN_COEF)
+      w.rec_coef = fused_bwd && h->bwd_lean != 0 && (kBwdLean & LEAN_COEF) != 0 ? 1 : 0;
       launch_fwd_pair(s, d, rp, (const float*)h->on, (const float*)h->tg, L, w, pair_hyp, stamp, hsched);
       if (stamp) {
         std::vector<uint32_t> st((size_t)8 * PST);
@@ -747,10 +754,18 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
     std::string bstamp_path;
     const bool bstamp = dwh_mode != 1 && env_item("MQ_DIAG", "bwd_stamp", &bstamp_path) && !bstamp_path.empty() &&
                         d.Tp <= BSTN - BSTH;
-    if (dwh_mode == 1) MQ_LDS(gru_bwd_fused_kernel<1>, dyn);
-    else MQ_LDS((gru_bwd_fused_kernel<0, true>), dyn);   // the larger of the two builds
-    if (dwh_mode == 1) launch_bwd_fused_dwh(dyn, s, d, rp, P0, L, w, h->pitch_rnn, l1);
-    else launch_bwd_fused(dim3(d.R), dyn, s, d, rp, P0, L, w, h->pitch_rnn, l1, bstamp);
+    // the lean per-step path rides with the row-pair forward's plan (MQ_PLAN bwd_lean=0: the classic step)
+    const bool lean = pair_fwd && h->bwd_lean != 0;
+    plan.bwd_lean = lean ? 1 : 0;
+    if (lean) {
+      if (dwh_mode == 1) MQ_LDS((gru_bwd_fused_kernel<1, false, kBwdLean>), dyn);
+      else MQ_LDS((gru_bwd_fused_kernel<0, true, kBwdLean>), dyn);   // the larger of the two builds
+    } else {
+      if (dwh_mode == 1) MQ_LDS(gru_bwd_fused_kernel<1>, dyn);
+      else MQ_LDS((gru_bwd_fused_kernel<0, true>), dyn);
+    }
+    if (dwh_mode == 1) launch_bwd_fused_dwh(dyn, s, d, rp, P0, L, w, h->pitch_rnn, l1, lean);
+    else launch_bwd_fused(dim3(d.R), dyn, s, d, rp, P0, L, w, h->pitch_rnn, l1, lean, bstamp);
     if (bstamp) {
       std::vector<uint32_t> st((size_t)8 * BSTN);
       MQ_HIP(hipMemcpyAsync(st.data(), w.GI, st.size() * 4, hipMemcpyDeviceToHost, s));

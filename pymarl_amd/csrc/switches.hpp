@@ -2,7 +2,7 @@
 // (INTEGRATION.md "Switches"). The default plan needs neither.
 //   MQ_PLAN  plan overrides for A/B runs and tests, read when a handle is created (mq_create / mc_create) unless
 //            noted: unfused_fwd, unfused_bwd, row_tiles=0|1, hyp_in_fwd=0|1, dwh_in_bwd=0|1, fwd_pair=0|1,
-//            pair_hyp_epi, mix_generic, lambda_path=1 (the TD(lambda) passes of the mixer tail even at
+//            bwd_lean=0|1, pair_hyp_epi, mix_generic, lambda_path=1 (the TD(lambda) passes of the mixer tail even at
 //            mq_config.td_lambda = 0); COMA (read per train()): coma_chain=0, coma_overlap=0
 //   MQ_DIAG  diagnostics and test hooks, read per train(): pair_stamp=<file> (the row-pair forward's s_memtime
 //            stamps), bwd_stamp=<file> (the fused BPTT's), hyp_sched=<hex> (the pair forward's in-loop hypernet tile

@@ -363,7 +363,7 @@ class QLearner:
     def last_plan(self):
         """Kernel variants the last train() launched (mq_last_plan): rows, fused_fwd, rw_fwd, fused_bwd, rw_bwd,
         inline_ids, hyper, mix, tiles, dwh (where QMIX's dW_hyper ran: "red1" or "bptt_grid"), td_lambda (1: the
-        mixer tail ran as the TD(lambda) passes)."""
+        mixer tail ran as the TD(lambda) passes), bwd_lean (1: the fused BPTT ran its lean per-step path)."""
         pl = _lib.MQPlan()
         _lib.check(self._handle.lib.mq_last_plan(self._handle.h, ctypes.byref(pl)))
         d = pl.as_dict()
