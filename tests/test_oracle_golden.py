@@ -37,6 +37,12 @@ def test_intermediates_and_params(golden_cases, name):
         if k == 0 and "step0_grads_clipped" in c.z:
             g = np.concatenate([v.ravel() for v in o.last["grads"].values()])
             assert rel_err(g, c.z["step0_grads_clipped"]) < 2e-6
+            # and every tensor on its own max (the global max is fc2.bias's, 10 to 1000 times the other tensors'):
+            # measured worst 4.05e-7 (hyper_w_1.bias of tiny_qmix); ten times that for the summation order of
+            # another torch build
+            ref = c.unflatten(c.z["step0_grads_clipped"])
+            for key, v in o.last["grads"].items():
+                assert rel_err(v, ref[key]) < 4e-6, (name, key)
         if "step_params" in c.z:
             assert rel_err(o.flat(), c.z["step_params"][k]) < 5e-5
     if "sqavg_final" in c.z:
