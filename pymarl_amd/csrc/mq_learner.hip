@@ -37,6 +37,7 @@
 #include "optim_kernels.hpp"
 #include "module_fwd.hpp"
 #include "switches.hpp"
+#include "step_plan.hpp"
 
 using namespace mq;
 
@@ -98,18 +99,10 @@ int lds_fits(const void* fn, size_t dyn, const char* what) {
       return set_err(MQ_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));        \
   } while (0)
 
-constexpr int kNsplitMax = 128;
 constexpr size_t kLambdaLdsMax = 64 * 1024;   // dynamic LDS of td_lambda_kernel (checked in mq_create)
 enum Phase { PH_FC1, PH_GI, PH_GRUF, PH_FC2, PH_HYP, PH_MIX, PH_GRUB, PH_DX1, PH_DW1, PH_DWH, PH_RED, PH_APPLY,
              PH_N };
 const char* kPhaseNames = "fc1;gi;gru_fwd;fc2;hyper;mix;gru_bwd;dx1;dw1;dwh;reduce;apply";
-
-int pick_rw(int R, int max_blocks) {
-  const int rws[4] = {1, 2, 4, 8};
-  for (int i = 0; i < 4; ++i)
-    if ((R + rws[i] - 1) / rws[i] <= max_blocks) return rws[i];
-  return 8;
-}
 
 }  // namespace
 
@@ -131,47 +124,16 @@ struct mq_handle {
   bool have_fb = false;
   Dims last;
   mq_plan plan{};
-  int nsplit_fc1 = 1, nsplit_mix = 1, nblk_bwd = 1, nblk_mix = 1, n_norm_part = 0;
-  // plan overrides (switches.hpp MQ_PLAN; A/B runs and tests, read once here)
-  bool force_unfused = plan_flag("unfused_fwd");       // the unfused forward (GEMMs around gru_fwd<RW>)
-  bool force_unfused_bwd = plan_flag("unfused_bwd");   // the unfused BPTT (gru_bwd<RW> + dX1 / dW1 GEMMs)
-  // rows up to which the fused BPTT (one row per workgroup, one workgroup per CU) is used: past the CU count the
-  // rows run as a second wave of workgroups, which still beats gru_bwd<2> + dX1 + dW1 at configs[3]'s shard
-  // (R = 320; round 3)
-  static constexpr int fused_bwd_rmax = 512;
-  // m-slices of the dW_hyper pass (A/B at cfg2, DESIGN §3: 4 / 8 / 16 / 32 -> 238.5 / 235.1 / 236.3 / 237.4 us)
-  int dwh_split = plan_int("dwh_split", 8);
-  // the row-tile MFMA forward / BPTT (gru_tiles.hpp) for batches past the one-row fused kernels (R > 512 rows);
-  // row_tiles=1 forces it on any batch it can take (tests), =0 turns it off (A/B: the unfused GEMM path)
-  int row_tiles = plan_int("row_tiles", -1);
+  int n_norm_part = 0;
+  PlanOverrides ov;   // MQ_PLAN, read once in mq_create (step_plan.hpp)
   bool dp = false;   // gradient buffer is summed across ranks between mq_forward_backward and mq_apply
   ncclComm_t comm = nullptr;   // mq_comm_attach / mq_comm_use: the library all-reduces the grad buffer itself
   int comm_world = 0;
   bool comm_owned = false;     // mq_comm_attach created it (freed on detach); mq_comm_use borrows the caller's
   hipStream_t side = nullptr;   // COMA: the actor's side stream (coma_host.hpp)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // QMIX hypernet workgroups appended to the fused forward's grid (gru_fwd_fused.hpp hyper_fwd_body) when the
-  // forward's 2R row-nets exceed two per CU: its second wave leaves CUs idle, and the hypernet fills them
-  // (configs[3]'s shard, R = 320: 0.364 -> 0.346 ms a step). hyp_in_fwd=0 never appends (and launches hyper_ws_kernel
-  // after the row-pair forward instead of running the hypernet inside it), =1 always (HYP bitwise the same either way)
-  int hyp_in_fwd = plan_int("hyp_in_fwd", -1);
-  // dW_hyper's tiles appended to the fused BPTT's grid (gru_bwd_fused.hpp, DWH = 1) when its rows exceed the CUs
-  // (a second wave of rows leaves CUs idle); dwh_in_bwd=0 never, =1 always (bitwise either way)
-  int dwh_in_bwd = plan_int("dwh_in_bwd", -1);
-  // the row-pair forward (gru_fwd_pair.hpp: both nets of a row in one workgroup, one per CU) when the rows fit one
-  // wave of workgroups; fwd_pair=0 keeps the one-row-net kernel, =1 forces the pair
-  int fwd_pair = plan_int("fwd_pair", -1);
-  // the fused BPTT's lean per-step path (gru_bwd_fused.hpp LEAN) behind the row-pair forward; bwd_lean=0 keeps the
-  // classic step (bitwise the same results)
-  int bwd_lean = plan_int("bwd_lean", -1);
-  bool pair_hyp_epi = plan_flag("pair_hyp_epi");   // the pair forward's hypernet as its epilogue, not on waves 4 / 5
-  // mix_kernel<false> where mix_kernel<true> (staged selection rows) would run
-  bool mix_generic = plan_flag("mix_generic");
-  // the TD(lambda) passes of the mixer tail (td_lambda_kernel.hpp) even at cfg.td_lambda = 0, where they compute the
-  // one-step target through the scan (A/B runs and tests)
-  bool lambda_path = plan_int("lambda_path", 0) != 0;
-  // their workspace, allocated only for a handle that runs them: y' and the lambda targets, [max_seq * max_batch]
-  // (no mixer: x n_agents) floats each
+  // the TD(lambda) passes' workspace, allocated only for a handle that runs them: y' and the lambda targets,
+  // [max_seq * max_batch] (no mixer: x n_agents) floats each
   float *YT = nullptr, *G = nullptr;
   bool have_lambda = false;   // the last step ran them (mq_copy_intermediate 4 / 5)
   int num_cu = 0;
@@ -212,21 +174,7 @@ void compute_layout(mq_handle* h) {
 int64_t align_up(int64_t x) { return (x + 63) & ~int64_t(63); }
 
 Dims make_dims(const mq_handle* h, const mq_replay* b) {
-  const mq_config& c = h->cfg;
-  Dims d;
-  d.n = c.n_agents; d.A = c.n_actions; d.O = c.obs_dim; d.S = c.state_dim; d.E = h->E; d.I = h->I; d.NH = h->NH;
-  d.B = b->batch_size; d.Tp = b->t_len; d.T = b->t_len - 1; d.R = d.B * d.n; d.M = d.T * d.B;
-  d.t_stride = b->t_stride;
-  d.last_action = c.obs_last_action; d.agent_id = c.obs_agent_id; d.mixer = c.mixer; d.double_q = c.double_q;
-  d.gamma = c.gamma;
-  d.huber = c.huber_delta;
-  d.dR = make_fastdiv((uint32_t)d.R);
-  d.dN = make_fastdiv((uint32_t)d.n);
-  d.dB = make_fastdiv((uint32_t)d.B);
-  d.dO = make_fastdiv((uint32_t)d.O);
-  d.dI = make_fastdiv((uint32_t)d.I);
-  d.dS = make_fastdiv((uint32_t)std::max(d.S, 1));
-  return d;
+  return mq::make_dims(h->cfg, b->batch_size, b->t_len, b->t_stride);
 }
 
 Rep make_rep(const mq_replay* b) {
@@ -297,10 +245,8 @@ hipError_t launch_gru_fwd(const Dims& d, const mq_handle* h, const Lay& L, const
 
 template <int RW>
 hipError_t launch_gru_bwd(const Dims& d, const Rep& rp, const mq_handle* h, const Lay& L, const Work& w,
-                          hipStream_t s, int* nblk) {
-  *nblk = (d.R + RW - 1) / RW;
-  const size_t dyn = ((size_t)2 * d.A * mq::H + d.A) * sizeof(float);
-  hipLaunchKernelGGL(gru_bwd_kernel<RW>, dim3(*nblk), dim3(512), dyn, s, d, rp, (const float*)h->on, L, w,
+                          hipStream_t s, int nblk, size_t dyn) {
+  hipLaunchKernelGGL(gru_bwd_kernel<RW>, dim3(nblk), dim3(512), dyn, s, d, rp, (const float*)h->on, L, w,
                      h->len_rnn);
   return hipGetLastError();
 }
@@ -308,9 +254,9 @@ hipError_t launch_gru_bwd(const Dims& d, const Rep& rp, const mq_handle* h, cons
 // The mixer tail's kernel for plan `mix` (MQ_MIX_*) in pass MODE (mix_kernels.hpp: the one-step tail, or one of the two
 // TD(lambda) passes around td_lambda_kernel).
 template <int MODE>
-void launch_mix(int mix, const mq_handle* h, const Dims& d, const Rep& rp, const Lay& L, const Work& w,
+void launch_mix(int mix, int nblk, const mq_handle* h, const Dims& d, const Rep& rp, const Lay& L, const Work& w,
                 int32_t* curmax, hipStream_t s) {
-  const dim3 grid(h->nblk_mix), block(256);
+  const dim3 grid(nblk), block(256);
   const float *P0 = h->on, *P1 = h->tg;
   if constexpr (MODE == MIX_ONE_STEP) {
     if (mix == MQ_MIX_FAST16)
@@ -394,6 +340,255 @@ int device_cus(mq_handle* h) {
   return h->num_cu;
 }
 
+// The tile kernels' <KQ1> instantiations (gru_tiles.hpp tile_kq1), named once: f(std::integral_constant<int, KQ1>).
+template <class F>
+void dispatch_kq1(int kq1, F&& f) {
+  if (kq1 == 8) f(std::integral_constant<int, 8>{});
+  else if (kq1 == 20) f(std::integral_constant<int, 20>{});
+  else if (kq1 == 40) f(std::integral_constant<int, 40>{});
+  else if (kq1 == 72) f(std::integral_constant<int, 72>{});
+  else f(std::integral_constant<int, 80>{});
+}
+
+// One train step's launches, phase by phase in stream order. Which kernels run is plan_step's answer `p`
+// (step_plan.hpp), fixed before the first launch; nothing here decides.
+struct Step {
+  mq_handle* h;
+  const Dims d;
+  const Rep rp;
+  const Lay L;
+  Work w;
+  int32_t* curmax;
+  hipStream_t s;
+  PhaseTimer pt;
+  const int64_t RT = (int64_t)d.Tp * d.R;
+
+  int forward(const StepPlan& p);
+  int hypernet(const StepPlan& p);
+  int mixer_tail(const StepPlan& p);
+  int bptt(const StepPlan& p);
+  int reduce(const StepPlan& p);
+};
+
+int Step::forward(const StepPlan& p) {
+  const float *P0 = h->on, *P1 = h->tg;
+  if (p.fwd == FWD_TILES) {
+    // row tiles of 32 (two M-tiles) per workgroup, both nets: the recurrence and fc1 / W_ih / fc2 on MFMA
+    pt.begin(PH_GRUF);
+    const dim3 grid(16 * (((d.R + TR_F - 1) / TR_F + 7) / 8));   // row tiles x 2 nets, XCD-paired (gru_tiles.hpp)
+    dispatch_kq1(p.kq1, [&](auto K) {
+      hipLaunchKernelGGL(gru_fwd_tile_kernel<decltype(K)::value>, grid, dim3(512), 0, s, d, rp, P0, P1, L, w);
+    });
+    MQ_HIP(hipGetLastError());
+  } else if (p.fwd != FWD_UNFUSED) {
+    // one row per workgroup: fc1 / W_ih / fc2 ride on the recurrence's idle matrix cores (gru_fwd_fused.hpp)
+    pt.begin(PH_GRUF);
+    if (p.hyp_place == HYP_FWD_GRID) {
+      launch_fwd_fused_hyp(s, d, rp, P0, P1, L, w);
+    } else if (p.fwd == FWD_PAIR) {
+      std::string stamp_path;   // diagnostic (MQ_DIAG pair_stamp=<file>): step stamps of the first 8 workgroups
+      const bool want_stamp = env_item("MQ_DIAG", "pair_stamp", &stamp_path) && !stamp_path.empty();
+      const int hsched = env_int("MQ_DIAG", "hyp_sched", kHypSched, 16);   // tuning: the in-loop tile schedule
+      const int pair_hyp = p.hyp_place == HYP_PAIR_WAVES ? 2 : p.hyp_place == HYP_PAIR_EPI ? 1 : 0;
+      // the stamp build has the 5-slot gather only: shapes past it run unstamped (never a partial gather)
+      const bool stamp = want_stamp && d.Tp <= 512 && FCH * d.O <= 256 * 5;
+      launch_fwd_pair(s, d, rp, P0, P1, L, w, pair_hyp, stamp, hsched);
+      if (stamp) {
+        std::vector<uint32_t> st((size_t)8 * PST);
+        MQ_HIP(hipMemcpyAsync(st.data(), w.slab_rnn, st.size() * 4, hipMemcpyDeviceToHost, s));
+        MQ_HIP(hipStreamSynchronize(s));
+        if (FILE* f = fopen(stamp_path.c_str(), "ab")) { fwrite(st.data(), 4, st.size(), f); fclose(f); }
+      }
+    } else {
+      launch_fwd_fused(dim3(d.R, 2), s, d, rp, P0, P1, L, w);
+    }
+    MQ_HIP(hipGetLastError());
+  } else {
+    pt.begin(PH_FC1);
+    {
+      // the dense agent-input copy (XIN) is dW1's operand, fused or not
+      Fc1Prob p{d, rp, h->on, h->tg, h->off[MQ_P_FC1_W], h->off[MQ_P_FC1_B], w.X1, w.XIN, RT};
+      MQ_HIP(launch_gemm(p, (int)RT, 2 * mq::H, 1, s));
+    }
+    pt.begin(PH_GI);
+    {
+      GiProb p{w.X1, h->on, h->tg, h->off[MQ_P_RNN_W_IH], h->off[MQ_P_RNN_B_IH], w.GI, RT};
+      MQ_HIP(launch_gemm(p, (int)RT, mq::G3, 2, s));
+    }
+    pt.begin(PH_GRUF);
+    {
+      const int rw_fwd = p.rw_fwd;
+      hipError_t e = rw_fwd == 1 ? launch_gru_fwd<1>(d, h, L, w, s)
+                   : rw_fwd == 2 ? launch_gru_fwd<2>(d, h, L, w, s)
+                   : rw_fwd == 4 ? launch_gru_fwd<4>(d, h, L, w, s)
+                                 : launch_gru_fwd<8>(d, h, L, w, s);
+      MQ_HIP(e);
+    }
+    pt.begin(PH_FC2);
+    {
+      Fc2Prob p{w.Hs, h->on, h->tg, h->off[MQ_P_FC2_W], h->off[MQ_P_FC2_B], w.Q, RT, d.A};
+      MQ_HIP(launch_gemm(p, (int)RT, d.A, 2, s));
+    }
+  }
+  return MQ_OK;
+}
+
+// The QMIX hypernet as a launch of its own (no forward carried it).
+int Step::hypernet(const StepPlan& p) {
+  if (p.hyp_place != HYP_OWN_LAUNCH) return MQ_OK;
+  pt.begin(PH_HYP);
+  if (p.hyper == MQ_HYP_WS) {
+    // wave-specialised weight streaming (hyper_kernel.hpp)
+    MQ_LDS(hyper_ws_kernel<0>, hyper_ws_lds_bytes(d.S));
+    hipLaunchKernelGGL(hyper_ws_kernel<0>, dim3((d.M + HYR - 1) / HYR, 2), dim3(HYWS_THREADS),
+                       hyper_ws_lds_bytes(d.S), s, d, rp, (const float*)h->on, (const float*)h->tg, L, w.HYP,
+                       w.S0);
+    MQ_HIP(hipGetLastError());
+  } else if (p.hyper == MQ_HYP_LDS) {
+    const size_t dyn = HyperGeom(d.S, d.NH).lds_bytes();
+    MQ_LDS(hyper_kernel<0>, dyn);
+    hipLaunchKernelGGL(hyper_kernel<0>, dim3((d.M + HYR - 1) / HYR, 2), dim3(256), dyn, s, d, rp,
+                       (const float*)h->on, (const float*)h->tg, L, w.HYP, w.S0);
+    MQ_HIP(hipGetLastError());
+  } else {
+    HypProb p{d, rp, L, h->on, h->tg, w.HYP, w.S0};
+    MQ_HIP(launch_gemm(p, d.M, d.NH, 2, s));
+  }
+  return MQ_OK;
+}
+
+int Step::mixer_tail(const StepPlan& p) {
+  const mq_config& c = h->cfg;
+  pt.begin(PH_MIX);
+  if (!p.lambda) {
+    launch_mix<MIX_ONE_STEP>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
+    MQ_HIP(hipGetLastError());
+  } else {
+    // TD(lambda): y' of every (t, b), the backward scan over t per episode, then the loss against its targets
+    const int k = c.mixer == MQ_MIXER_NONE ? d.n : 1;
+    const size_t dyn = td_lambda_lds_bytes(d.T, k);
+    MQ_LDS(td_lambda_kernel, dyn);
+    launch_mix<MIX_LAMBDA_TARGETS>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
+    MQ_HIP(hipGetLastError());
+    const float lg = (float)((double)c.td_lambda * (double)c.gamma);
+    const float og = (float)((1.0 - (double)c.td_lambda) * (double)c.gamma);
+    hipLaunchKernelGGL(td_lambda_kernel, dim3(d.B), dim3(256), dyn, s, d, rp, (const float*)h->YT, h->G, k, lg, og);
+    MQ_HIP(hipGetLastError());
+    launch_mix<MIX_LAMBDA_LOSS>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
+    MQ_HIP(hipGetLastError());
+  }
+  return MQ_OK;
+}
+
+// BPTT, with dX1 / dW1 as GEMMs behind the unfused recurrence.
+int Step::bptt(const StepPlan& p) {
+  pt.begin(PH_GRUB);
+  const float* P0 = h->on;
+  const int64_t l1 = (int64_t)mq::H * d.I + mq::H;
+  const size_t dyn = ((size_t)2 * d.A * mq::H + d.A) * sizeof(float);   // the one-row kernels' fc2 staging
+  if (p.fwd == FWD_TILES) {
+    // the two-role (chain / weight-gradient waves) BPTT, 512 threads
+    dispatch_kq1(p.kq1, [&](auto K) {
+      hipLaunchKernelGGL(gru_bwd_split_kernel<decltype(K)::value>, dim3(p.nblk_bwd), dim3(512), 0, s, d, rp, P0, L, w,
+                         h->len_rnn, l1);
+    });
+    MQ_HIP(hipGetLastError());
+  } else if (p.fused_bwd) {
+    // one row per workgroup: dW_hh / dW_ih / dX1 / dW1 on the chain's idle matrix cores (gru_bwd_fused.hpp)
+    if (p.dwh_in_bwd) {   // dW_hyper's tiles in this grid: the reduction's dW_hyper blocks, same geometry
+      w.dwh_tj = p.tj;
+      w.dwh_ns = p.ns;
+      w.dwh_n = p.ndwh;
+      w.dwh_len = h->len_mix;
+    }
+    // diagnostic (MQ_DIAG bwd_stamp=<file>): step stamps of the first 8 workgroups
+    std::string bstamp_path;
+    const bool bstamp = !p.dwh_in_bwd && env_item("MQ_DIAG", "bwd_stamp", &bstamp_path) && !bstamp_path.empty() &&
+                        d.Tp <= BSTN - BSTH;
+    if (p.lean) {
+      if (p.dwh_in_bwd) MQ_LDS((gru_bwd_fused_kernel<1, false, kBwdLean>), dyn);
+      else MQ_LDS((gru_bwd_fused_kernel<0, true, kBwdLean>), dyn);   // the larger of the two builds
+    } else {
+      if (p.dwh_in_bwd) MQ_LDS(gru_bwd_fused_kernel<1>, dyn);
+      else MQ_LDS((gru_bwd_fused_kernel<0, true>), dyn);
+    }
+    if (p.dwh_in_bwd) launch_bwd_fused_dwh(dyn, s, d, rp, P0, L, w, h->pitch_rnn, l1, p.lean);
+    else launch_bwd_fused(dim3(d.R), dyn, s, d, rp, P0, L, w, h->pitch_rnn, l1, p.lean, bstamp);
+    if (bstamp) {
+      std::vector<uint32_t> st((size_t)8 * BSTN);
+      MQ_HIP(hipMemcpyAsync(st.data(), w.GI, st.size() * 4, hipMemcpyDeviceToHost, s));
+      MQ_HIP(hipStreamSynchronize(s));
+      if (FILE* f = fopen(bstamp_path.c_str(), "ab")) { fwrite(st.data(), 4, st.size(), f); fclose(f); }
+    }
+    MQ_HIP(hipGetLastError());
+  } else {
+    {
+      const int rw_bwd = p.rw_bwd, nblk = p.nblk_bwd;
+      if (rw_bwd == 1) MQ_LDS(gru_bwd_kernel<1>, dyn);
+      else if (rw_bwd == 2) MQ_LDS(gru_bwd_kernel<2>, dyn);
+      else MQ_LDS(gru_bwd_kernel<4>, dyn);
+      hipError_t e = rw_bwd == 1 ? launch_gru_bwd<1>(d, rp, h, L, w, s, nblk, dyn)
+                   : rw_bwd == 2 ? launch_gru_bwd<2>(d, rp, h, L, w, s, nblk, dyn)
+                                 : launch_gru_bwd<4>(d, rp, h, L, w, s, nblk, dyn);
+      MQ_HIP(e);
+    }
+    pt.begin(PH_DX1);
+    {
+      Dx1Prob p{w.dGI, h->on + h->off[MQ_P_RNN_W_IH], w.X1, w.dP1, RT};
+      MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));
+    }
+    pt.begin(PH_DW1);
+    {
+      const int ns = p.dw1_ns;
+      Dw1Prob p{d.I, w.dP1, w.XIN, w.slab_fc1, RT, ns};
+      MQ_HIP(launch_gemm(p, mq::H, d.I, ns, s));
+    }
+  }
+  return MQ_OK;
+}
+
+// The slab reductions into the flat gradient buffer; pass 1 shares its launch with dW_hyper (dwh_red1_kernel) unless
+// dW_hyper's tiles rode in the BPTT's grid.
+int Step::reduce(const StepPlan& p) {
+  const bool qmix = h->cfg.mixer == MQ_MIXER_QMIX;
+  RedBuilder rb(w.red_tmp);
+  rb.add(w.slab_fc1, p.nsplit_fc1, (int64_t)mq::H * d.I + mq::H, h->grad + h->off[MQ_P_FC1_W], true);
+  if (p.fused_bwd) {   // [W_ih | W_hh] in the BPTT's C-tile order (red_dst), then the biases and fc2
+    const int64_t lm = 2LL * mq::G3 * mq::H;
+    rb.add(w.slab_rnn, p.nblk_bwd, lm, h->grad + h->off[MQ_P_RNN_W_IH], true, h->pitch_rnn, false, 1);
+    rb.add(w.slab_rnn + lm, p.nblk_bwd, h->len_rnn - lm, h->grad + h->off[MQ_P_RNN_W_IH] + lm, true, h->pitch_rnn);
+  } else {
+    rb.add(w.slab_rnn, p.nblk_bwd, h->len_rnn, h->grad + h->off[MQ_P_RNN_W_IH], true);
+  }
+  if (qmix) {
+    // dW_hyper's few m-slice slabs go straight to pass 2 (they are written in the same launch as pass 1)
+    const bool direct = rb.add(w.slab_mix, p.nsplit_mix, h->len_mix, h->grad + h->off[MQ_P_HW1_W], true, 0, true);
+    if (p.dwh_in_red1 && !direct)   // pass-1 blocks would read slabs the dW_hyper blocks of the same grid still write
+      return set_err(MQ_ERR_STATE, "dW_hyper fused with reduction pass 1 needs a direct slab region");
+    rb.add(w.slab_v2, p.nblk_mix, d.E + 1, h->grad + h->off[MQ_P_V2_W], true);
+  }
+  rb.add(w.loss_part, p.nblk_mix, MQ_NSUMS, h->grad + h->P, false);
+  if (p.dwh_in_red1) {
+    pt.begin(PH_DWH);
+    const int ndwh_pad = (p.ndwh + 15) / 16 * 16;
+    hipLaunchKernelGGL(dwh_red1_kernel<4>, dim3(ndwh_pad + rb.b1), dim3(256), 0, s, d, L, (const float*)w.dHYP,
+                       (const float*)w.S0, w.slab_mix, h->len_mix, p.ns, p.tj, p.ndwh, ndwh_pad, rb.pl);
+    MQ_HIP(hipGetLastError());
+    pt.begin(PH_RED);
+  } else {
+    pt.begin(PH_RED);
+    if (rb.b1 > 0) {
+      hipLaunchKernelGGL(red_pass1_kernel, dim3(rb.b1), dim3(256), 0, s, rb.pl);
+      MQ_HIP(hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(red_pass2_kernel, dim3(rb.b2), dim3(256), 0, s, rb.pl, w.norm_part);
+  MQ_HIP(hipGetLastError());
+  h->n_norm_part = rb.b2;
+  pt.end();
+  return MQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -422,16 +617,17 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
     return set_err(MQ_ERR_ARG, "td_lambda must be in [0, 1] (0: the reference's one-step target)");
   // the scan stages an episode's inputs in dynamic LDS (td_lambda_kernel.hpp): kept within what a launch may ask for
   // without raising the kernel's dynamic-LDS attribute
-  if ((c.td_lambda > 0.0f || plan_int("lambda_path", 0) != 0) &&
+  const PlanOverrides ov = read_plan_overrides();
+  if ((c.td_lambda > 0.0f || ov.lambda_path) &&
       td_lambda_lds_bytes(c.max_seq - 1, c.mixer == MQ_MIXER_NONE ? c.n_agents : 1) > kLambdaLdsMax)
     return set_err(MQ_ERR_ARG, "td_lambda: max_seq " + std::to_string(c.max_seq) + " needs more than " +
                                    std::to_string(kLambdaLdsMax) + " B of LDS for the TD(lambda) scan");
 
   mq_handle* h = new mq_handle();
   h->cfg = c;
-  h->E = c.mixer == MQ_MIXER_QMIX ? c.mixing_embed_dim : 0;
-  h->I = c.obs_dim + (c.obs_last_action ? c.n_actions : 0) + (c.obs_agent_id ? c.n_agents : 0);
-  h->NH = h->E * (c.n_agents + 3);
+  h->ov = ov;
+  const Dims dmax = mq::make_dims(c, c.max_batch, c.max_seq, c.max_seq);   // E, I, NH as every step derives them
+  h->E = dmax.E; h->I = dmax.I; h->NH = dmax.NH;
   compute_layout(h);
 
   const int64_t n = c.n_agents, A = c.n_actions, Hd = mq::H;
@@ -488,7 +684,7 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
   w.XIN = base + offs[18];
   w.S0 = base + offs[19];
   w.curmax = h->curmax_ws;
-  if (c.td_lambda > 0.0f || h->lambda_path) {
+  if (c.td_lambda > 0.0f || ov.lambda_path) {
     const int64_t len = align_up((int64_t)c.max_seq * c.max_batch * (c.mixer == MQ_MIXER_NONE ? n : 1));
     e = hipMalloc((void**)&h->YT, 2 * len * sizeof(float));
     if (e != hipSuccess) {
@@ -549,316 +745,22 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
     return set_err(MQ_ERR_STATE, "training needs online, target, grad, sq_avg and stats bound (mq_bind)");
   int rc = check_batch(h, batch);
   if (rc) return rc;
-  const Dims d = make_dims(h, batch);
-  const Rep rp = make_rep(batch);
-  const Lay L = make_lay(h);
-  Work w = h->w;
-  int32_t* curmax = h->curmax_user ? h->curmax_user : h->curmax_ws;
-  const int64_t RT = (int64_t)d.Tp * d.R;
-  PhaseTimer pt{h, s};
-  const mq_config& c = h->cfg;
-
-  mq_plan plan{};
-  plan.rows = d.R;
-  plan.inline_ids = rp.nids > 0 ? 1 : 0;
-  const int rw_bwd = std::min(2, pick_rw(d.R, 256));
-  const int kq1 = tile_kq1(d.O);
-  const bool tiles = tiles_ok(d.I, d.O, d.A, d.n, d.Tp, RT) && !h->force_unfused && !h->force_unfused_bwd &&
-                     (h->row_tiles == 1 || (h->row_tiles < 0 && d.R > 512));
-  const bool fused_bwd = !tiles && d.R <= h->fused_bwd_rmax && fused_bwd_ok(d.I, d.O, d.A, d.n, RT) &&
-                         !h->force_unfused_bwd;
-  const int rw_fwd = pick_rw(d.R, 512);
-  bool hyp_in_fwd = false;
-  bool pair_fwd = false;   // the row-pair forward runs (plan.fused_fwd = 2)
-  plan.tiles = tiles ? 1 : 0;
-  if (tiles) {
-    // row tiles of 32 (two M-tiles) per workgroup, both nets: the recurrence and fc1 / W_ih / fc2 on MFMA
-    pt.begin(PH_GRUF);
-    const dim3 grid(16 * (((d.R + TR_F - 1) / TR_F + 7) / 8));   // row tiles x 2 nets, XCD-paired (gru_tiles.hpp)
-    const float *P0 = h->on, *P1 = h->tg;
-    if (kq1 == 8) hipLaunchKernelGGL(gru_fwd_tile_kernel<8>, grid, dim3(512), 0, s, d, rp, P0, P1, L, w);
-    else if (kq1 == 20) hipLaunchKernelGGL(gru_fwd_tile_kernel<20>, grid, dim3(512), 0, s, d, rp, P0, P1, L, w);
-    else if (kq1 == 40) hipLaunchKernelGGL(gru_fwd_tile_kernel<40>, grid, dim3(512), 0, s, d, rp, P0, P1, L, w);
-    else if (kq1 == 72) hipLaunchKernelGGL(gru_fwd_tile_kernel<72>, grid, dim3(512), 0, s, d, rp, P0, P1, L, w);
-    else hipLaunchKernelGGL(gru_fwd_tile_kernel<80>, grid, dim3(512), 0, s, d, rp, P0, P1, L, w);
-    MQ_HIP(hipGetLastError());
-  } else if (rw_fwd == 1 && fused_fwd_ok(d.I, d.O, d.A, d.n, RT) && !h->force_unfused) {
-    plan.fused_fwd = 1;
-    // one row per workgroup: fc1 / W_ih / fc2 ride on the recurrence's idle matrix cores (gru_fwd_fused.hpp)
-    pt.begin(PH_GRUF);
-    const bool two_waves = device_cus(h) > 0 && d.R > h->num_cu;   // 2R row-nets at two per CU
-    // the row-pair forward when the rows fit one wave of workgroups (MQ_PLAN fwd_pair=1 forces it, =0 keeps the one-row-net
-    // kernel); hyp_in_fwd=1 asks for the one-row-net kernel with the hypernet appended to its grid
-    const bool pair = h->hyp_in_fwd != 1 && pair_fwd_ok(d.I, d.O, d.A, d.n, RT) &&
-                      (h->fwd_pair == 1 || (h->fwd_pair < 0 && !two_waves && device_cus(h) > 0));
-    hyp_in_fwd = !pair && (h->hyp_in_fwd == 1 || (h->hyp_in_fwd < 0 && two_waves)) && c.mixer == MQ_MIXER_QMIX &&
-                 hyper_ws_ok(d.S, d.E, d.NH, d.M) && hyf_ok(d.S, d.E, d.NH, d.M);
-    if (hyp_in_fwd) {
-      plan.hyper = MQ_HYP_WS;
-      launch_fwd_fused_hyp(s, d, rp, (const float*)h->on, (const float*)h->tg, L, w);
-    } else if (pair) {
-      plan.fused_fwd = 2;
-      pair_fwd = true;
-      // the QMIX hypernet as the pair kernel's epilogue (hyp_in_fwd=0 keeps hyper_ws_kernel after it)
-      hyp_in_fwd = h->hyp_in_fwd != 0 && c.mixer == MQ_MIXER_QMIX && hyper_ws_ok(d.S, d.E, d.NH, d.M) &&
-                   hyf_ok(d.S, d.E, d.NH, d.M);
-      if (hyp_in_fwd) plan.hyper = MQ_HYP_WS;
-      std::string stamp_path;   // diagnostic (MQ_DIAG pair_stamp=<file>): step stamps of the first 8 workgroups
-      const bool want_stamp = env_item("MQ_DIAG", "pair_stamp", &stamp_path) && !stamp_path.empty();
-      const int hsched = env_int("MQ_DIAG", "hyp_sched", kHypSched, 16);   // tuning: the in-loop tile schedule
-      // on waves 4 / 5 inside the kernel when every hypernet block has a workgroup, else as its epilogue
-      // (pair_hyp_epi forces the epilogue)
-      const int pair_hyp = !hyp_in_fwd ? 0 : (2 * ((d.M + 31) / 32) <= d.R && !h->pair_hyp_epi) ? 2 : 1;
-      // the stamp build has the 5-slot gather only: shapes past it run unstamped (never a partial gather)
-      const bool stamp = want_stamp && d.Tp <= 512 && FCH * d.O <= 256 * 5;
-      // the fused BPTT's lean path reads the coefficient record (gru_bwd_fused.hpp LEAN_COEF)
-      w.rec_coef = fused_bwd && h->bwd_lean != 0 && (kBwdLean & LEAN_COEF) != 0 ? 1 : 0;
-      launch_fwd_pair(s, d, rp, (const float*)h->on, (const float*)h->tg, L, w, pair_hyp, stamp, hsched);
-      if (stamp) {
-        std::vector<uint32_t> st((size_t)8 * PST);
-        MQ_HIP(hipMemcpyAsync(st.data(), w.slab_rnn, st.size() * 4, hipMemcpyDeviceToHost, s));
-        MQ_HIP(hipStreamSynchronize(s));
-        if (FILE* f = fopen(stamp_path.c_str(), "ab")) { fwrite(st.data(), 4, st.size(), f); fclose(f); }
-      }
-    } else {
-      launch_fwd_fused(dim3(d.R, 2), s, d, rp, (const float*)h->on, (const float*)h->tg, L, w);
-    }
-    MQ_HIP(hipGetLastError());
-  } else {
-    plan.rw_fwd = rw_fwd;
-    pt.begin(PH_FC1);
-    {
-      // the dense agent-input copy (XIN) is dW1's operand, fused or not
-      Fc1Prob p{d, rp, h->on, h->tg, h->off[MQ_P_FC1_W], h->off[MQ_P_FC1_B], w.X1, w.XIN, RT};
-      MQ_HIP(launch_gemm(p, (int)RT, 2 * mq::H, 1, s));
-    }
-    pt.begin(PH_GI);
-    {
-      GiProb p{w.X1, h->on, h->tg, h->off[MQ_P_RNN_W_IH], h->off[MQ_P_RNN_B_IH], w.GI, RT};
-      MQ_HIP(launch_gemm(p, (int)RT, mq::G3, 2, s));
-    }
-    pt.begin(PH_GRUF);
-    {
-      hipError_t e = rw_fwd == 1 ? launch_gru_fwd<1>(d, h, L, w, s)
-                   : rw_fwd == 2 ? launch_gru_fwd<2>(d, h, L, w, s)
-                   : rw_fwd == 4 ? launch_gru_fwd<4>(d, h, L, w, s)
-                                 : launch_gru_fwd<8>(d, h, L, w, s);
-      MQ_HIP(e);
-    }
-    pt.begin(PH_FC2);
-    {
-      Fc2Prob p{w.Hs, h->on, h->tg, h->off[MQ_P_FC2_W], h->off[MQ_P_FC2_B], w.Q, RT, d.A};
-      MQ_HIP(launch_gemm(p, (int)RT, d.A, 2, s));
-    }
-  }
-  h->nblk_mix = (d.M + 3) / 4;
-  if (c.mixer == MQ_MIXER_QMIX && !hyp_in_fwd) {
-    pt.begin(PH_HYP);
-    if (hyper_ws_ok(d.S, d.E, d.NH, d.M)) {
-      plan.hyper = MQ_HYP_WS;
-      // wave-specialised weight streaming (hyper_kernel.hpp)
-      MQ_LDS(hyper_ws_kernel<0>, hyper_ws_lds_bytes(d.S));
-      hipLaunchKernelGGL(hyper_ws_kernel<0>, dim3((d.M + HYR - 1) / HYR, 2), dim3(HYWS_THREADS),
-                         hyper_ws_lds_bytes(d.S), s, d, rp, (const float*)h->on, (const float*)h->tg, L, w.HYP,
-                         w.S0);
-      MQ_HIP(hipGetLastError());
-    } else if (hyper_ok(d.S, d.NH)) {
-      plan.hyper = MQ_HYP_LDS;
-      const size_t dyn = HyperGeom(d.S, d.NH).lds_bytes();
-      MQ_LDS(hyper_kernel<0>, dyn);
-      hipLaunchKernelGGL(hyper_kernel<0>, dim3((d.M + HYR - 1) / HYR, 2), dim3(256), dyn, s, d, rp,
-                         (const float*)h->on, (const float*)h->tg, L, w.HYP, w.S0);
-      MQ_HIP(hipGetLastError());
-    } else {
-      plan.hyper = MQ_HYP_GEMM;
-      HypProb p{d, rp, L, h->on, h->tg, w.HYP, w.S0};
-      MQ_HIP(launch_gemm(p, d.M, d.NH, 2, s));
-    }
-  }
-  pt.begin(PH_MIX);
-  {
-    const bool fast = d.n <= 16 && d.E <= 64;   // mix_kernel serves the rest (n > 16 or A > 32)
-    const bool stream = mix_stream_ok(d.n, d.A) && !h->mix_generic;
-    plan.mix = fast && d.A <= 16 ? MQ_MIX_FAST16 : fast && d.A <= 32 ? MQ_MIX_FAST32 : stream ? MQ_MIX_STREAM
-                                                                                             : MQ_MIX_GENERIC;
-    const bool lambda = h->YT != nullptr;   // cfg.td_lambda > 0 or MQ_PLAN lambda_path=1 (mq_create)
-    plan.td_lambda = lambda ? 1 : 0;
-    if (!lambda) {
-      launch_mix<MIX_ONE_STEP>(plan.mix, h, d, rp, L, w, curmax, s);
-      MQ_HIP(hipGetLastError());
-    } else {
-      // TD(lambda): y' of every (t, b), the backward scan over t per episode, then the loss against its targets
-      const int k = c.mixer == MQ_MIXER_NONE ? d.n : 1;
-      const size_t dyn = td_lambda_lds_bytes(d.T, k);
-      MQ_LDS(td_lambda_kernel, dyn);
-      launch_mix<MIX_LAMBDA_TARGETS>(plan.mix, h, d, rp, L, w, curmax, s);
-      MQ_HIP(hipGetLastError());
-      const float lg = (float)((double)c.td_lambda * (double)c.gamma);
-      const float og = (float)((1.0 - (double)c.td_lambda) * (double)c.gamma);
-      hipLaunchKernelGGL(td_lambda_kernel, dim3(d.B), dim3(256), dyn, s, d, rp, (const float*)h->YT, h->G, k, lg, og);
-      MQ_HIP(hipGetLastError());
-      launch_mix<MIX_LAMBDA_LOSS>(plan.mix, h, d, rp, L, w, curmax, s);
-      MQ_HIP(hipGetLastError());
-    }
-  }
-  pt.begin(PH_GRUB);
-  bool dwh_in_bwd = false;
-  int dwh_mode = 0;   // where dW_hyper runs (mq_plan.dwh)
-  // dW_hyper's m-slices (A/B at cfg2: 4 / 8 / 16 / 32 -> 238.5 / 235.1 / 236.3 / 237.4 us, round 1)
-  const int dwh_ns = std::max(1, std::min({h->dwh_split, kRedZ, (d.M + 1) / 2}));
-  plan.fused_bwd = fused_bwd ? 1 : 0;
-  plan.rw_bwd = fused_bwd || tiles ? 0 : rw_bwd;
-  if (tiles) {
-    const int nblk = (d.R + TR_B - 1) / TR_B;
-    h->nblk_bwd = nblk;
-    h->nsplit_fc1 = nblk;
-    const int64_t l1 = (int64_t)mq::H * d.I + mq::H;
-    const float* P0 = h->on;
-    // the two-role (chain / weight-gradient waves) BPTT, 512 threads
-#define MQ_BWD_TILE(K) \
-  hipLaunchKernelGGL(gru_bwd_split_kernel<K>, dim3(nblk), dim3(512), 0, s, d, rp, P0, L, w, h->len_rnn, l1);
-    if (kq1 == 8) { MQ_BWD_TILE(8) }
-    else if (kq1 == 20) { MQ_BWD_TILE(20) }
-    else if (kq1 == 40) { MQ_BWD_TILE(40) }
-    else if (kq1 == 72) { MQ_BWD_TILE(72) }
-    else { MQ_BWD_TILE(80) }
-#undef MQ_BWD_TILE
-    MQ_HIP(hipGetLastError());
-  } else if (fused_bwd) {
-    // one row per workgroup: dW_hh / dW_ih / dX1 / dW1 on the chain's idle matrix cores (gru_bwd_fused.hpp)
-    const bool many = device_cus(h) > 0 && d.R > h->num_cu;   // a second wave of rows leaves CUs idle
-    h->nblk_bwd = d.R;
-    h->nsplit_fc1 = h->nblk_bwd;
-    const size_t dyn = ((size_t)2 * d.A * mq::H + d.A) * sizeof(float);
-    // dW_hyper: appended to the BPTT's grid when its rows exceed the CUs (mode 1: the second wave of rows leaves
-    // CUs idle), else beside pass 1 of the reduction (mode 0); MQ_PLAN dwh_in_bwd=0|1 forces one. (Round 6: its
-    // tiles on the BPTT's chain waves in the kernel's tail, idle while the producers reduce the last chunk, made the
-    // BPTT 14 us longer against the 8.6 us they took out of the reduction's launch: four waves per CU leave each
-    // tile's load round trips exposed. Removed.)
-    if (c.mixer == MQ_MIXER_QMIX) {
-      const int tj = (d.NH + DWH_T - 1) / DWH_T, ts = (d.S + 1 + DWH_T - 1) / DWH_T;
-      dwh_mode = h->dwh_in_bwd >= 0 ? (h->dwh_in_bwd ? 1 : 0) : many ? 1 : 0;
-      if (dwh_mode != 0) {   // the reduction's dW_hyper blocks, same geometry (see dwh_fused below)
-        w.dwh_tj = tj;
-        w.dwh_ns = dwh_ns;
-        w.dwh_n = tj * ts * dwh_ns;
-        w.dwh_len = h->len_mix;
-        h->nsplit_mix = dwh_ns;
-      }
-    }
-    dwh_in_bwd = dwh_mode != 0;
-    plan.dwh = dwh_mode;
-    const float* P0 = (const float*)h->on;
-    const int64_t l1 = (int64_t)mq::H * d.I + mq::H;
-    // diagnostic (MQ_DIAG bwd_stamp=<file>): step stamps of the first 8 workgroups
-    std::string bstamp_path;
-    const bool bstamp = dwh_mode != 1 && env_item("MQ_DIAG", "bwd_stamp", &bstamp_path) && !bstamp_path.empty() &&
-                        d.Tp <= BSTN - BSTH;
-    // the lean per-step path rides with the row-pair forward's plan (MQ_PLAN bwd_lean=0: the classic step)
-    const bool lean = pair_fwd && h->bwd_lean != 0;
-    plan.bwd_lean = lean ? 1 : 0;
-    if (lean) {
-      if (dwh_mode == 1) MQ_LDS((gru_bwd_fused_kernel<1, false, kBwdLean>), dyn);
-      else MQ_LDS((gru_bwd_fused_kernel<0, true, kBwdLean>), dyn);   // the larger of the two builds
-    } else {
-      if (dwh_mode == 1) MQ_LDS(gru_bwd_fused_kernel<1>, dyn);
-      else MQ_LDS((gru_bwd_fused_kernel<0, true>), dyn);
-    }
-    if (dwh_mode == 1) launch_bwd_fused_dwh(dyn, s, d, rp, P0, L, w, h->pitch_rnn, l1, lean);
-    else launch_bwd_fused(dim3(d.R), dyn, s, d, rp, P0, L, w, h->pitch_rnn, l1, lean, bstamp);
-    if (bstamp) {
-      std::vector<uint32_t> st((size_t)8 * BSTN);
-      MQ_HIP(hipMemcpyAsync(st.data(), w.GI, st.size() * 4, hipMemcpyDeviceToHost, s));
-      MQ_HIP(hipStreamSynchronize(s));
-      if (FILE* f = fopen(bstamp_path.c_str(), "ab")) { fwrite(st.data(), 4, st.size(), f); fclose(f); }
-    }
-    MQ_HIP(hipGetLastError());
-  } else {
-    {
-      // RW >= 4 spills the 96 role registers + per-row prefetch sets at 512 threads; cap at 2
-      const size_t dyn = ((size_t)2 * d.A * mq::H + d.A) * sizeof(float);
-      if (rw_bwd == 1) MQ_LDS(gru_bwd_kernel<1>, dyn);
-      else if (rw_bwd == 2) MQ_LDS(gru_bwd_kernel<2>, dyn);
-      else MQ_LDS(gru_bwd_kernel<4>, dyn);
-      hipError_t e = rw_bwd == 1 ? launch_gru_bwd<1>(d, rp, h, L, w, s, &h->nblk_bwd)
-                   : rw_bwd == 2 ? launch_gru_bwd<2>(d, rp, h, L, w, s, &h->nblk_bwd)
-                                 : launch_gru_bwd<4>(d, rp, h, L, w, s, &h->nblk_bwd);
-      MQ_HIP(e);
-    }
-    pt.begin(PH_DX1);
-    {
-      Dx1Prob p{w.dGI, h->on + h->off[MQ_P_RNN_W_IH], w.X1, w.dP1, RT};
-      MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));
-    }
-    pt.begin(PH_DW1);
-    {
-      const int tiles = (d.I + Dw1Prob::BN - 1) / Dw1Prob::BN;
-      int ns = (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RT / 256));
-      ns = std::max(1, std::min(ns, (512 + tiles - 1) / tiles));
-      // keep every split non-empty under krange_split's GBK rounding
-      int64_t chunk = ((RT + ns - 1) / ns + GBK - 1) / GBK * GBK;
-      ns = (int)((RT + chunk - 1) / chunk);
-      h->nsplit_fc1 = ns;
-      Dw1Prob p{d.I, w.dP1, w.XIN, w.slab_fc1, RT, ns};
-      MQ_HIP(launch_gemm(p, mq::H, d.I, ns, s));
-    }
-  }
-  // dW_hyper runs fused with pass 1 of the reduction (dwh_red1_kernel), unless its tiles rode in the BPTT's grid
-  const bool dwh_fused = c.mixer == MQ_MIXER_QMIX && !dwh_in_bwd;
-  {
-    int tj = 0, ts = 0, ns = 0, ndwh = 0;
-    if (dwh_fused) {
-      tj = (d.NH + DWH_T - 1) / DWH_T;
-      ts = (d.S + 1 + DWH_T - 1) / DWH_T;
-      // pass 1 shares this launch with dW_hyper, so dW_hyper's slabs must go straight to pass 2: at most kRedZ
-      ns = dwh_ns;
-      h->nsplit_mix = ns;
-      ndwh = tj * ts * ns;
-    }
-    RedBuilder rb(w.red_tmp);
-    rb.add(w.slab_fc1, h->nsplit_fc1, (int64_t)mq::H * d.I + mq::H, h->grad + h->off[MQ_P_FC1_W], true);
-    if (fused_bwd) {   // [W_ih | W_hh] in the BPTT's C-tile order (red_dst), then the biases and fc2
-      const int64_t lm = 2LL * mq::G3 * mq::H;
-      rb.add(w.slab_rnn, h->nblk_bwd, lm, h->grad + h->off[MQ_P_RNN_W_IH], true, h->pitch_rnn, false, 1);
-      rb.add(w.slab_rnn + lm, h->nblk_bwd, h->len_rnn - lm, h->grad + h->off[MQ_P_RNN_W_IH] + lm, true, h->pitch_rnn);
-    } else {
-      rb.add(w.slab_rnn, h->nblk_bwd, h->len_rnn, h->grad + h->off[MQ_P_RNN_W_IH], true);
-    }
-    if (c.mixer == MQ_MIXER_QMIX) {
-      // dW_hyper's few m-slice slabs go straight to pass 2 (they are written in the same launch as pass 1)
-      const bool direct = rb.add(w.slab_mix, h->nsplit_mix, h->len_mix, h->grad + h->off[MQ_P_HW1_W], true, 0, true);
-      if (dwh_fused && !direct)   // pass-1 blocks would read slabs the dW_hyper blocks of the same grid still write
-        return set_err(MQ_ERR_STATE, "dW_hyper fused with reduction pass 1 needs a direct slab region");
-      rb.add(w.slab_v2, h->nblk_mix, d.E + 1, h->grad + h->off[MQ_P_V2_W], true);
-    }
-    rb.add(w.loss_part, h->nblk_mix, MQ_NSUMS, h->grad + h->P, false);
-    if (dwh_fused) {
-      pt.begin(PH_DWH);
-      const int ndwh_pad = (ndwh + 15) / 16 * 16;
-      hipLaunchKernelGGL(dwh_red1_kernel<4>, dim3(ndwh_pad + rb.b1), dim3(256), 0, s, d, L, (const float*)w.dHYP,
-                         (const float*)w.S0, w.slab_mix, h->len_mix, ns, tj, ndwh, ndwh_pad, rb.pl);
-      MQ_HIP(hipGetLastError());
-      pt.begin(PH_RED);
-    } else {
-      pt.begin(PH_RED);
-      if (rb.b1 > 0) {
-        hipLaunchKernelGGL(red_pass1_kernel, dim3(rb.b1), dim3(256), 0, s, rb.pl);
-        MQ_HIP(hipGetLastError());
-      }
-    }
-    hipLaunchKernelGGL(red_pass2_kernel, dim3(rb.b2), dim3(256), 0, s, rb.pl, w.norm_part);
-    MQ_HIP(hipGetLastError());
-    h->n_norm_part = rb.b2;
-  }
-  pt.end();
+  Step st{h, make_dims(h, batch), make_rep(batch), make_lay(h), h->w, h->curmax_user ? h->curmax_user : h->curmax_ws,
+          s, PhaseTimer{h, s}};
+  // a handle with the TD(lambda) workspace runs the lambda passes: cfg.td_lambda > 0 or MQ_PLAN lambda_path=1
+  const StepPlan p = plan_step(h->cfg, h->ov, st.d, st.rp.nids > 0, h->YT != nullptr, device_cus(h));
+  st.w.rec_coef = p.rec_coef;
+  if ((rc = st.forward(p)) || (rc = st.hypernet(p)) || (rc = st.mixer_tail(p)) || (rc = st.bptt(p)) ||
+      (rc = st.reduce(p)))
+    return rc;
   if (h->comm) {   // native data parallelism: the whole [grads | sums] buffer, summed over the ranks in stream order
     const ncclResult_t r = ncclAllReduce(h->grad, h->grad, (size_t)(h->P + MQ_NSUMS), ncclFloat, ncclSum, h->comm, s);
     if (r != ncclSuccess) return set_err(MQ_ERR_HIP, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
   }
-  h->last = d;
-  h->plan = plan;
+  h->last = st.d;
+  h->plan = p.report;
   h->have_fb = true;
-  h->have_lambda = plan.td_lambda != 0;
+  h->have_lambda = p.lambda;
   return MQ_OK;
 }
 

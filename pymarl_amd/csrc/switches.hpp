@@ -1,9 +1,11 @@
 // The library's environment switches: two variables, each a comma-separated list of `key` or `key=value` items
 // (INTEGRATION.md "Switches"). The default plan needs neither.
-//   MQ_PLAN  plan overrides for A/B runs and tests, read when a handle is created (mq_create / mc_create) unless
-//            noted: unfused_fwd, unfused_bwd, row_tiles=0|1, hyp_in_fwd=0|1, dwh_in_bwd=0|1, fwd_pair=0|1,
+//   MQ_PLAN  plan overrides for A/B runs and tests. The QMIX / VDN / IQL learner's items are read once per handle, by
+//            read_plan_overrides (step_plan.hpp) in mq_create, into the PlanOverrides that plan_step takes:
+//            unfused_fwd, unfused_bwd, row_tiles=0|1, hyp_in_fwd=0|1, dwh_in_bwd=0|1, dwh_split=<n>, fwd_pair=0|1,
 //            bwd_lean=0|1, pair_hyp_epi, mix_generic, lambda_path=1 (the TD(lambda) passes of the mixer tail even at
-//            mq_config.td_lambda = 0); COMA (read per train()): coma_chain=0, coma_overlap=0
+//            mq_config.td_lambda = 0); COMA's where they are used (coma_host.hpp): coma_chain=0 (mc_create),
+//            coma_overlap=0 (per train())
 //   MQ_DIAG  diagnostics and test hooks, read per train(): pair_stamp=<file> (the row-pair forward's s_memtime
 //            stamps), bwd_stamp=<file> (the fused BPTT's), hyp_sched=<hex> (the pair forward's in-loop hypernet tile
 //            schedule), coma_trace (the COMA chain's phase times), coma_fault=<workgroup> (a chain workgroup that
