@@ -133,12 +133,40 @@ int mq_comm_create(const uint8_t* id, int32_t rank, int32_t world, void** nccl_c
 int mq_comm_free(void* nccl_comm);
 int mq_update_targets(mq_handle* h, void* stream);
 
+/* Prioritized episode replay (PER), an opt-in the reference lacks. Priorities live on the device and never reach the
+ * host: mq_per_sample draws, the next train step weights its loss and writes the new priorities back.
+ *
+ * mq_per_sample: stratified draw of `batch` episodes (duplicates allowed) from slots [0, n_live) of prio (raw
+ * priorities, > 0), u[batch] uniform in [0, 1), all fp32:
+ *   q_i = prio_i^alpha (alpha == 1: prio_i), cum = inclusive scan of q, total = cum[n_live - 1]
+ *   tau_b = ((float)b + u[b]) * (total / (float)batch);  ids[b] = the first i with cum[i] > tau_b, at most n_live - 1
+ *   weights[b] = (n_live * q_ids[b] / total)^(-beta), divided by their maximum (beta == 0: exactly 1)
+ * One launch on `stream`; ids int64 [batch] and weights [batch] are device outputs. MQ_ERR_ARG: alpha < 0 or NaN,
+ * beta outside [0, 1], n_live < 1 or > MQ_PER_MAX_LIVE, batch < 1, a NULL pointer. */
+enum { MQ_PER_MAX_LIVE = 32768 };
+int mq_per_sample(const float* prio, int32_t n_live, const float* u, int32_t batch, float alpha, float beta,
+                  int64_t* ids, float* weights, void* stream);
+/* Arm the NEXT mq_forward_backward / mq_train_step as a PER step; that step disarms it again, and so does a NULL
+ * `per` (never sticky). The step's batch must carry device episode ids (mq_replay.ep_ids, ep_ids_host NULL): they
+ * are the slots of prio it writes. The PER step:
+ *   loss = sum_b weights[b] sum_t loss(td * mask) / sum mask (stats[0]; the other stats stay unweighted), dy of every
+ *   row times its weights[b];
+ *   afterwards prio[ids[b]] = sum_t |td * mask| / max(sum_t mask, 1) + eps (no mixer: the agents' sum over
+ *   n_agents * sum_t mask), and *prio_max = max(*prio_max, those).
+ * weights [batch_size], prio [n_prio], prio_max [1]: device pointers, borrowed until that step has been queued.
+ * MQ_ERR_ARG: eps <= 0 or NaN, n_prio < 1, a NULL pointer; at the step: a communicator attached or data parallelism
+ * set (not supported), or a batch without device ids. */
+typedef struct mq_per { const float* weights; float* prio; float* prio_max; int64_t n_prio; float eps; } mq_per;
+int mq_set_per(mq_handle* h, const mq_per* per);
+
 /* Copy an intermediate of the last mq_forward_backward into dst (device): 0 = online mac_out [t][b*n+a][A],
  * 1 = target mac_out (same layout), 2 = dQ/dchosen [t][b*n+a] (unnormalised), 3 = online relu(fc1) activations
  * [t][b*n+a][64]. Returns element count in *count.
  * After a step that ran the TD(lambda) passes (mq_plan.td_lambda = 1; MQ_ERR_STATE otherwise): 4 = y', the target
  * network's mixed value at step t + 1, as [t][b] (no mixer: [t][b*n+a], one value per agent), t < t_len - 1;
- * 5 = the lambda targets in the same layout. */
+ * 5 = the lambda targets in the same layout.
+ * After a prioritized-replay step (mq_plan.per = 1; MQ_ERR_STATE otherwise): 6 = |td * mask| of every transition,
+ * unweighted, as [t][b] (no mixer: summed over the agents), t < t_len - 1: what the priority write-back summed. */
 int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, void* stream);
 
 /* BasicMAC.forward(ep_batch, t) for every episode of `batch`: h_in/h_out [batch*n][64] (h_in may equal
@@ -180,6 +208,8 @@ typedef struct mq_plan {
   int32_t bwd_lean;      /* 1: the fused BPTT ran its lean per-step path (walked chain addresses, per-chunk fc2-gradient
                             inputs, dW2 / db2 in registers): the default behind the row-pair forward (fused_fwd = 2,
                             fused_bwd = 1); MQ_PLAN bwd_lean=0 keeps the classic step (bitwise the same results) */
+  int32_t per;           /* 1: a prioritized-replay step (mq_set_per): the loss-bearing mixer pass ran in its PER form
+                            and the priority write-back followed it */
 } mq_plan;
 int mq_last_plan(const mq_handle* h, mq_plan* out);
 

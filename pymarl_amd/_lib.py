@@ -26,7 +26,7 @@ EXPORTS = [
     "mq_last_error", "mq_create", "mq_destroy", "mq_param_offsets", "mq_bind", "mq_forward_backward", "mq_apply",
     "mq_train_step", "mq_update_targets", "mq_copy_intermediate", "mq_mac_forward", "mq_agent_forward",
     "mq_greedy_actions", "mq_set_timing", "mq_phase_times", "mq_phase_names", "mq_set_data_parallel",
-    "mq_last_plan", "mq_qmix_forward",
+    "mq_last_plan", "mq_qmix_forward", "mq_per_sample", "mq_set_per",
     # include/mc_coma.h
     "mc_create", "mc_destroy", "mc_param_offsets", "mc_bind", "mc_train_step", "mc_update_targets", "mc_policy",
     "mc_copy_intermediate", "mc_set_timing", "mc_phase_times", "mc_last_critic_path", "mq_comm_unique_id", "mq_comm_attach",
@@ -80,10 +80,19 @@ class MCConfig(ctypes.Structure):
 
 class MQPlan(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("rows", "fused_fwd", "rw_fwd", "fused_bwd", "rw_bwd", "inline_ids",
-                                               "hyper", "mix", "tiles", "dwh", "td_lambda", "bwd_lean")]
+                                               "hyper", "mix", "tiles", "dwh", "td_lambda", "bwd_lean", "per")]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class MQPer(ctypes.Structure):
+    """mq_per: one prioritized-replay step's weights and the priority storage it writes (device pointers)."""
+    _fields_ = [("weights", ctypes.c_void_p), ("prio", ctypes.c_void_p), ("prio_max", ctypes.c_void_p),
+                ("n_prio", ctypes.c_int64), ("eps", ctypes.c_float)]
+
+
+PER_MAX_LIVE = 32768   # MQ_PER_MAX_LIVE: live episodes one mq_per_sample draw supports
 
 
 HYP_NAMES = {0: "none", 1: "ws", 2: "lds", 3: "gemm"}
@@ -131,6 +140,8 @@ def load(required=True):
         "mq_set_data_parallel": ([vp, i32], ctypes.c_int),
         "mq_last_plan": ([vp, ctypes.POINTER(MQPlan)], ctypes.c_int),
         "mq_qmix_forward": ([vp, i32, i32, i32, vp, vp, vp, i32, vp], ctypes.c_int),
+        "mq_per_sample": ([vp, i32, vp, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp], ctypes.c_int),
+        "mq_set_per": ([vp, ctypes.POINTER(MQPer)], ctypes.c_int),
         "mc_critic_forward_workspace": ([ctypes.POINTER(MCConfig), i32, i32], i64),
         "mc_critic_forward": ([vp, ctypes.POINTER(MCConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp], ctypes.c_int),
         "mq_phase_times": ([vp, ctypes.POINTER(ctypes.c_float), i32, ctypes.POINTER(i32)], ctypes.c_int),

@@ -310,6 +310,44 @@ class SampledBatch(EpisodeBatch):
         return self
 
 
+class PrioritizedBatch(SampledBatch):
+    """A PrioritizedReplayBuffer sample: the storage, DEVICE episode ids and importance weights (both written by the
+    sampler kernel, never read by the host) and t_len, the longest live episode of the buffer (the host cannot know
+    which episodes were drawn without a sync; the surplus steps are fully masked). The learner trains on it as a PER
+    step: weighted loss, then the priority write-back into `source.prio` (QLearner.train)."""
+
+    ep_ids_np = None   # there is no host copy of the ids
+
+    def __init__(self, source, ep_ids, weights, t_len):
+        self.source = source
+        self._ep_ids_dev = ep_ids
+        self.weights = weights
+        self.t_len = int(t_len)
+        EpisodeBatch.__init__(self, source.scheme, source.groups, int(ep_ids.shape[0]), self.t_len,
+                              data=SN(transition_data=_LazyGather(self, True), episode_data=_LazyGather(self, False)),
+                              preprocess=None, device=source.device)
+
+    def __getitem__(self, item):
+        if isinstance(item, tuple) and len(item) == 2 and isinstance(item[0], slice) and item[0] == slice(None) \
+                and isinstance(item[1], slice) and item[1].start in (None, 0) and item[1].step in (None, 1):
+            stop = self.t_len if item[1].stop is None else min(int(item[1].stop), self.t_len)
+            return PrioritizedBatch(self.source, self._ep_ids_dev, self.weights, stop)
+        return super().__getitem__(item)
+
+    def max_t_filled(self):
+        return self.t_len
+
+    def shard(self, rank, world):
+        raise ValueError("a prioritized-replay batch cannot be sharded: data-parallel learners are not supported "
+                         "with PrioritizedReplayBuffer")
+
+    def to(self, device):
+        if _same_device(device, self.device):
+            return self
+        raise ValueError("a prioritized-replay batch lives on its buffer's device ({}) and cannot move to {}: the "
+                         "learner writes the priorities back into that buffer".format(self.device, device))
+
+
 class _LazyGather(dict):
     def __init__(self, batch, transition):
         super().__init__()
@@ -440,4 +478,84 @@ class ReplayBuffer(EpisodeBatch):
 
     def __repr__(self):
         return "ReplayBuffer. {}/{} episodes. Keys:{} Groups:{}".format(
+            self.episodes_in_buffer, self.buffer_size, self.scheme.keys(), self.groups.keys())
+
+
+class PrioritizedReplayBuffer(ReplayBuffer):
+    """Prioritized episode replay (an opt-in the reference lacks): episodes are drawn in proportion to
+    priority^per_alpha, the batch carries importance weights (N P(i))^-beta / max, and the learner's train step writes
+    each drawn episode's new priority, mean |TD error| over its unmasked transitions + per_eps, back into `prio`
+    (include/mq_learner.h: mq_per_sample, mq_set_per). New episodes get `prio_max`, the largest priority seen so far
+    (1.0 at first). `prio` [buffer_size] and `prio_max` [1] live on the buffer's device and are never read by the host
+    on the sample / train path; `u`, one uniform number per draw (stratified sampling), comes from a device generator
+    seeded with `seed` (None: torch's initial seed), drawn U_BLOCK batches at a time so that a step does not pay a
+    generator launch of its own. `beta` is a plain attribute: the run loop may anneal it.
+    The buffer must be on a HIP device to be sampled: like the learner, there is no CPU path."""
+
+    U_BLOCK = 64   # batches of u per generator call
+
+    def __init__(self, scheme, groups, buffer_size, max_seq_length, preprocess=None, device="cpu", per_alpha=0.6,
+                 per_beta=0.4, per_eps=1e-6, seed=None):
+        super().__init__(scheme, groups, buffer_size, max_seq_length, preprocess=preprocess, device=device)
+        self.alpha = float(per_alpha)
+        self.beta = float(per_beta)
+        self.eps = float(per_eps)
+        self.seed = th.initial_seed() if seed is None else int(seed)
+        self.prio = th.ones(buffer_size, dtype=th.float32, device=self.device)
+        self.prio_max = th.ones(1, dtype=th.float32, device=self.device)
+        self._gen = None
+        self._u_block, self._u_next = None, 0
+
+    def to(self, device):
+        super().to(device)
+        self.prio = self.prio.to(device)
+        self.prio_max = self.prio_max.to(device)
+        self._gen = None
+        self._u_block = None
+        return self
+
+    def insert_episode_batch(self, ep_batch):
+        fits = self.buffer_index + ep_batch.batch_size <= self.buffer_size
+        sl = slice(self.buffer_index, self.buffer_index + ep_batch.batch_size)
+        super().insert_episode_batch(ep_batch)   # a batch that wraps comes back here in two parts
+        if fits:
+            self.prio[sl] = self.prio_max   # device-side broadcast: no host read
+
+    def load_arrays(self, arrays, n_episodes=None):
+        super().load_arrays(arrays, n_episodes)
+        n = n_episodes if n_episodes is not None else len(next(iter(arrays.values())))
+        self.prio[:n] = self.prio_max
+
+    def sample(self, batch_size, u=None):
+        """`batch_size` draws (duplicates allowed) as a PrioritizedBatch. u: optional [batch_size] numbers in [0, 1),
+        one per stratum, in place of the generator's (tests)."""
+        from .. import _lib
+        assert self.can_sample(batch_size)
+        _lib.require_gpu(self.prio)
+        dev = self.prio.device
+        if u is None:
+            if self._gen is None:
+                self._gen = th.Generator(device=dev)
+                self._gen.manual_seed(self.seed)
+            blk = self._u_block
+            if blk is None or blk.shape[1] != batch_size or self._u_next >= blk.shape[0]:
+                blk = self._u_block = th.rand(self.U_BLOCK, batch_size, generator=self._gen, device=dev,
+                                              dtype=th.float32)
+                self._u_next = 0
+            u = blk[self._u_next]
+            self._u_next += 1
+        else:
+            u = th.as_tensor(u, dtype=th.float32, device=dev).contiguous()
+            assert u.numel() == batch_size
+        ids = th.empty(batch_size, dtype=th.int64, device=dev)
+        weights = th.empty(batch_size, dtype=th.float32, device=dev)
+        lib = _lib.load()
+        _lib.check(lib.mq_per_sample(_lib.ptr(self.prio), self.episodes_in_buffer, _lib.ptr(u), batch_size,
+                                     self.alpha, self.beta, _lib.ptr(ids), _lib.ptr(weights), _lib.stream_ptr(dev)))
+        # the longest live episode: host lengths, so no sync (not the longest SAMPLED one, which only the device knows)
+        t_len = int(min(self.episode_lengths[:self.episodes_in_buffer].max(), self.max_seq_length))
+        return PrioritizedBatch(self, ids, weights, t_len)
+
+    def __repr__(self):
+        return "PrioritizedReplayBuffer. {}/{} episodes. Keys:{} Groups:{}".format(
             self.episodes_in_buffer, self.buffer_size, self.scheme.keys(), self.groups.keys())

@@ -20,6 +20,13 @@ MQ_DEV float eluf(float x) { return x > 0.0f ? x : expm1f(x); }
 // y'[m] (YT: [m], or [m][n] without a mixer); MIX_LAMBDA_LOSS does the online side, the loss and the mixer backward
 // with target = G[m], the scan's output, in place of r + gamma (1 - term) y'.
 enum { MIX_ONE_STEP = 0, MIX_LAMBDA_TARGETS = 1, MIX_LAMBDA_LOSS = 2 };
+// Prioritized replay (per_kernels.hpp) is a flag on the two loss-bearing passes, MIX_ONE_STEP | MIX_PER and
+// MIX_LAMBDA_LOSS | MIX_PER: the row's loss term and dy are each multiplied once by its episode's importance weight
+// W[b], and |td m| of the row (unweighted; without a mixer the sum over its agent lanes) goes to TDA[m] for the
+// priority write-back. At W == 1 every value is the plain pass's, bit for bit. The plain instantiations are the
+// kernels they always were (same symbols, same argument block, same code).
+enum { MIX_PER = 4 };
+constexpr int mix_pass(int mode) { return mode & 3; }
 
 // The lambda target of row m on this lane (VDN: one per row; no mixer: one per agent lane).
 MQ_DEV float lambda_target(const float* __restrict__ G, int mixer, bool valid, int m, int n, int lane) {
@@ -29,8 +36,26 @@ MQ_DEV float lambda_target(const float* __restrict__ G, int mixer, bool valid, i
 }
 
 // The two lambda passes take (YT, G) as trailing kernel arguments; the one-step kernels take none (LAM is empty), so
-// their argument block is the one they always had.
+// their argument block is the one they always had. A PER pass takes (W, TDA) after them.
 MQ_DEV void lambda_args(float*& YT, const float*& G, float* yt, const float* g) { YT = yt; G = g; }
+// Row b's importance weight (a plain pass: the constant 1, never used).
+template <bool PER>
+MQ_DEV float per_weight(const float* __restrict__ W, bool valid, int b) {
+  if constexpr (PER) return valid ? W[b] : 0.0f;
+  else return 1.0f;
+}
+MQ_DEV void tail_args(float*&, const float*&, const float*&, float*&) {}
+MQ_DEV void tail_args(float*& YT, const float*& G, const float*&, float*&, float* yt, const float* g) {
+  lambda_args(YT, G, yt, g);
+}
+MQ_DEV void tail_args(float*&, const float*&, const float*& W, float*& TDA, const float* wt, float* tda) {
+  W = wt; TDA = tda;
+}
+MQ_DEV void tail_args(float*& YT, const float*& G, const float*& W, float*& TDA, float* yt, const float* g,
+                      const float* wt, float* tda) {
+  lambda_args(YT, G, yt, g);
+  W = wt; TDA = tda;
+}
 
 struct MixOut {
   float y, pre, hid, wf_raw, hv;   // lane-e intermediates of the online mixer (QMIX)
@@ -73,13 +98,17 @@ constexpr int MIXS_MAX = 1024;   // n * A staged per item
 constexpr int MIXS_NPT = MIXS_MAX / 256;
 inline bool mix_stream_ok(int n, int A) { return n * A <= MIXS_MAX; }
 
-template <bool STREAM, int MODE = MIX_ONE_STEP, typename... LAM>
+template <bool STREAM, int FULL = MIX_ONE_STEP, typename... LAM>
 __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* __restrict__ P0,
                                                   const float* __restrict__ P1, Lay L, Work w, int32_t* curmax_out,
                                                   LAM... lam) {
+  constexpr int MODE = mix_pass(FULL);
+  constexpr bool PER = (FULL & MIX_PER) != 0;
   float* YT = nullptr;
   const float* G = nullptr;
-  if constexpr (MODE != MIX_ONE_STEP) lambda_args(YT, G, lam...);
+  const float* W = nullptr;   // PER: the batch rows' importance weights [B], and |td m| out [m]
+  float* TDA = nullptr;
+  tail_args(YT, G, W, TDA, lam...);
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + wv;
   const int n = d.n, A = d.A, E = d.E, R = d.R, NH = d.NH;
@@ -108,6 +137,7 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
     rew = rp.reward[slot];
     term = (float)rp.term[slot];
   }
+  [[maybe_unused]] const float wb = per_weight<PER>(W, valid, b);   // in flight with every other load
   if constexpr (MODE == MIX_LAMBDA_LOSS) {   // the chosen-action values only: pass A made the selection
     if (valid && lane < n) {
       const int at = (int)rp.actions[(ep * d.t_stride + t) * n + lane];
@@ -241,7 +271,12 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
     const float td = y - target;
     const float mtd = td * mask;
     l2 = td_loss(mtd, d.huber); msk = mask; abs_ = fabsf(mtd); qs = y * mask; tg = target * mask;
-    const float dy = td_dy(mtd, mask, d.huber);   // d sum loss(td*m) / d Q_tot
+    float dy = td_dy(mtd, mask, d.huber);   // d sum loss(td*m) / d Q_tot
+    if constexpr (PER) {
+      l2 *= wb;
+      dy *= wb;
+      if (valid && lane == 0) TDA[m] = abs_;
+    }
     // ---- QMIX backward (lanes e < E)
     float dpre = 0.0f;
     if (valid && lane < E) {
@@ -290,7 +325,7 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
     if constexpr (MODE == MIX_LAMBDA_LOSS) target = lambda_target(G, d.mixer, valid, m, n, lane);
     const float td = y - target;
     const float mtd = td * mask;
-    const float dy = td_dy(mtd, mask, d.huber);
+    float dy = td_dy(mtd, mask, d.huber);
     if (d.mixer == MQ_MIXER_VDN) {
       l2 = td_loss(mtd, d.huber); msk = mask; abs_ = fabsf(mtd); qs = y * mask; tg = target * mask;
     } else {
@@ -300,6 +335,11 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
       abs_ = wave_sum(on ? fabsf(mtd) : 0.0f);
       qs = wave_sum(on ? y * mask : 0.0f);
       tg = wave_sum(on ? target * mask : 0.0f);
+    }
+    if constexpr (PER) {
+      l2 *= wb;
+      dy *= wb;
+      if (valid && lane == 0) TDA[m] = abs_;
     }
     if (valid && lane < n) w.dch[(int64_t)t * R + b * n + lane] = dy;
     __syncthreads();   // match the QMIX branch's barrier count
@@ -344,11 +384,14 @@ struct alignas(16) MixScratch {
   float w1s[MN][65];   // |hyper_w_1| rows of the online mixer, for dLoss/dchosen
 };
 
-template <int MA, int MN, int MODE = MIX_ONE_STEP>
+template <int MA, int MN, int FULL = MIX_ONE_STEP>
 MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__ P0, const float* __restrict__ P1,
                          const Lay& L, const Work& w, int32_t* curmax_out, int m, int lane, const float* hon,
                          const float* htg, MixScratch<MN>& sc, float* red_slot, float* v2_slot,
-                         float* __restrict__ YT, const float* __restrict__ G) {
+                         float* __restrict__ YT, const float* __restrict__ G, const float* __restrict__ W = nullptr,
+                         float* __restrict__ TDA = nullptr) {
+  constexpr int MODE = mix_pass(FULL);
+  constexpr bool PER = (FULL & MIX_PER) != 0;
   constexpr bool ONLINE = MODE != MIX_LAMBDA_TARGETS;   // chosen values, online mix, loss, mixer backward
   constexpr bool TARGET = MODE != MIX_LAMBDA_LOSS;      // double-Q selection and the target-side mix
   const int n = d.n, A = d.A, E = d.E, R = d.R, NH = d.NH;
@@ -363,6 +406,7 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
     b = m - t * d.B;
     ep = rp.ep(b);
   }
+  [[maybe_unused]] const float wb = per_weight<PER>(W, valid, b);   // in flight with every other load
   const int64_t slot = ep * d.t_stride + t;
   const float* Qon = w.Q;
   const float* Qtg = w.Q + d.RT() * A;
@@ -502,7 +546,12 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
     const float td = y - target;
     const float mtd = td * mask;
     l2 = td_loss(mtd, d.huber); msk = mask; abs_ = fabsf(mtd); qs = y * mask; tg = target * mask;
-    const float dy = td_dy(mtd, mask, d.huber);
+    float dy = td_dy(mtd, mask, d.huber);
+    if constexpr (PER) {
+      l2 *= wb;
+      dy *= wb;
+      if (valid && lane == 0) TDA[m] = abs_;
+    }
     float dpre = 0.0f;
     if (e_lane) {
       const float wf = fabsf(xon[0]);
@@ -538,7 +587,7 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
     if constexpr (!TARGET) target = lambda_target(G, d.mixer, valid, m, n, lane);
     const float td = y - target;
     const float mtd = td * mask;
-    const float dy = td_dy(mtd, mask, d.huber);
+    float dy = td_dy(mtd, mask, d.huber);
     if (d.mixer == MQ_MIXER_VDN) {
       l2 = td_loss(mtd, d.huber); msk = mask; abs_ = fabsf(mtd); qs = y * mask; tg = target * mask;
     } else {
@@ -548,6 +597,11 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
       abs_ = wave_sum(on ? fabsf(mtd) : 0.0f);
       qs = wave_sum(on ? y * mask : 0.0f);
       tg = wave_sum(on ? target * mask : 0.0f);
+    }
+    if constexpr (PER) {
+      l2 *= wb;
+      dy *= wb;
+      if (valid && lane == 0) TDA[m] = abs_;
     }
     if (agent_lane) w.dch[(int64_t)t * R + b * n + lane] = dy;
     __syncthreads();
@@ -560,13 +614,16 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
   v2_slot[lane] = dv2;
 }
 
-template <int MA, int MN, int MODE = MIX_ONE_STEP, typename... LAM>
+template <int MA, int MN, int FULL = MIX_ONE_STEP, typename... LAM>
 __global__ __launch_bounds__(256) void mix_fast_kernel(Dims d, Rep rp, const float* __restrict__ P0,
                                                        const float* __restrict__ P1, Lay L, Work w,
                                                        int32_t* curmax_out, LAM... lam) {
+  constexpr int MODE = mix_pass(FULL);
   float* YT = nullptr;
   const float* G = nullptr;
-  if constexpr (MODE != MIX_ONE_STEP) lambda_args(YT, G, lam...);
+  const float* W = nullptr;
+  float* TDA = nullptr;
+  tail_args(YT, G, W, TDA, lam...);
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + wv;
   const int E = d.E, NH = d.NH;
@@ -576,7 +633,8 @@ __global__ __launch_bounds__(256) void mix_fast_kernel(Dims d, Rep rp, const flo
   __shared__ float v2red[4][65];
   const float* hon = w.HYP + (int64_t)m * NH;
   const float* htg = w.HYP + ((int64_t)d.M + m) * NH;
-  mix_fast_row<MA, MN, MODE>(d, rp, P0, P1, L, w, curmax_out, m, lane, hon, htg, sc[wv], red[wv], v2red[wv], YT, G);
+  mix_fast_row<MA, MN, FULL>(d, rp, P0, P1, L, w, curmax_out, m, lane, hon, htg, sc[wv], red[wv], v2red[wv], YT, G, W,
+                             TDA);
   if constexpr (MODE == MIX_LAMBDA_TARGETS) return;   // no loss terms in this pass
   __syncthreads();
   if (threadIdx.x < 8) {

@@ -8,6 +8,8 @@
 //   hyper    gemm  QMIX hypernet outputs of state[:, :-1] / state[:, 1:] both nets (QMIX only)
 //   mix      per (t, episode): chosen gather, double-Q select, mixer fwd, TD, masked L2 sums, mixer bwd
 //            (TD(lambda) targets, mq_config.td_lambda > 0: three launches, td_lambda_kernel.hpp)
+//            (prioritized replay, mq_set_per: the loss-bearing pass in its PER form, then per_priority_kernel;
+//            mq_per_sample draws the next batch, per_kernels.hpp)
 //   gru_bwd  recur BPTT; dW_hh, dW_ih, dW2 and biases accumulated in-kernel, dGI written out
 //   dx1      gemm  dP1 = (dGI W_ih) * [X1 > 0]
 //   dw1      gemm  [dW1 | db1] = dP1^T xin                                split-K
@@ -32,6 +34,7 @@
 #include "gru_tiles.hpp"
 #include "mix_kernels.hpp"
 #include "td_lambda_kernel.hpp"
+#include "per_kernels.hpp"
 #include "hyper_kernel.hpp"
 #include "dwh_kernel.hpp"
 #include "optim_kernels.hpp"
@@ -136,6 +139,12 @@ struct mq_handle {
   // [max_seq * max_batch] (no mixer: x n_agents) floats each
   float *YT = nullptr, *G = nullptr;
   bool have_lambda = false;   // the last step ran them (mq_copy_intermediate 4 / 5)
+  // prioritized replay (mq_set_per): armed for the next step only; TDA [max_seq * max_batch] is the tail's |td m|
+  // record, allocated by the first mq_set_per
+  mq_per per{};
+  bool per_armed = false;
+  float* TDA = nullptr;
+  bool have_per = false;   // the last step was a PER step (mq_copy_intermediate 6)
   int num_cu = 0;
   // timing: a ring of `slots` steps x PH_N (start, stop) event pairs; phases outside `mask` are not recorded
   int slots = 0;
@@ -282,6 +291,46 @@ void launch_mix(int mix, int nblk, const mq_handle* h, const Dims& d, const Rep&
     else
       hipLaunchKernelGGL((mix_kernel<false, MODE, float*, const float*>), grid, block, 0, s, d, rp, P0, P1, L, w,
                          curmax, YT, G);
+  }
+}
+
+// The loss-bearing pass MODE (MIX_ONE_STEP or MIX_LAMBDA_LOSS) in its PER form: (W, TDA) trail the pass's arguments.
+template <int MODE>
+void launch_mix_per(int mix, int nblk, const mq_handle* h, const Dims& d, const Rep& rp, const Lay& L, const Work& w,
+                    int32_t* curmax, hipStream_t s) {
+  const dim3 grid(nblk), block(256);
+  const float *P0 = h->on, *P1 = h->tg;
+  const float* W = h->per.weights;
+  float* TDA = h->TDA;
+  constexpr int M = MODE | MIX_PER;
+  if constexpr (MODE == MIX_ONE_STEP) {
+    if (mix == MQ_MIX_FAST16)
+      hipLaunchKernelGGL((mix_fast_kernel<16, 16, M, const float*, float*>), grid, block, 0, s, d, rp, P0, P1, L, w,
+                         curmax, W, TDA);
+    else if (mix == MQ_MIX_FAST32)
+      hipLaunchKernelGGL((mix_fast_kernel<32, 16, M, const float*, float*>), grid, block, 0, s, d, rp, P0, P1, L, w,
+                         curmax, W, TDA);
+    else if (mix == MQ_MIX_STREAM)
+      hipLaunchKernelGGL((mix_kernel<true, M, const float*, float*>), grid, block, 0, s, d, rp, P0, P1, L, w, curmax,
+                         W, TDA);
+    else
+      hipLaunchKernelGGL((mix_kernel<false, M, const float*, float*>), grid, block, 0, s, d, rp, P0, P1, L, w, curmax,
+                         W, TDA);
+  } else {
+    float* YT = h->YT;
+    const float* G = h->G;
+    if (mix == MQ_MIX_FAST16)
+      hipLaunchKernelGGL((mix_fast_kernel<16, 16, M, float*, const float*, const float*, float*>), grid, block, 0, s,
+                         d, rp, P0, P1, L, w, curmax, YT, G, W, TDA);
+    else if (mix == MQ_MIX_FAST32)
+      hipLaunchKernelGGL((mix_fast_kernel<32, 16, M, float*, const float*, const float*, float*>), grid, block, 0, s,
+                         d, rp, P0, P1, L, w, curmax, YT, G, W, TDA);
+    else if (mix == MQ_MIX_STREAM)
+      hipLaunchKernelGGL((mix_kernel<true, M, float*, const float*, const float*, float*>), grid, block, 0, s, d, rp,
+                         P0, P1, L, w, curmax, YT, G, W, TDA);
+    else
+      hipLaunchKernelGGL((mix_kernel<false, M, float*, const float*, const float*, float*>), grid, block, 0, s, d, rp,
+                         P0, P1, L, w, curmax, YT, G, W, TDA);
   }
 }
 
@@ -461,7 +510,8 @@ int Step::mixer_tail(const StepPlan& p) {
   const mq_config& c = h->cfg;
   pt.begin(PH_MIX);
   if (!p.lambda) {
-    launch_mix<MIX_ONE_STEP>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
+    if (p.per) launch_mix_per<MIX_ONE_STEP>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
+    else launch_mix<MIX_ONE_STEP>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
     MQ_HIP(hipGetLastError());
   } else {
     // TD(lambda): y' of every (t, b), the backward scan over t per episode, then the loss against its targets
@@ -474,7 +524,13 @@ int Step::mixer_tail(const StepPlan& p) {
     const float og = (float)((1.0 - (double)c.td_lambda) * (double)c.gamma);
     hipLaunchKernelGGL(td_lambda_kernel, dim3(d.B), dim3(256), dyn, s, d, rp, (const float*)h->YT, h->G, k, lg, og);
     MQ_HIP(hipGetLastError());
-    launch_mix<MIX_LAMBDA_LOSS>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
+    if (p.per) launch_mix_per<MIX_LAMBDA_LOSS>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
+    else launch_mix<MIX_LAMBDA_LOSS>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
+    MQ_HIP(hipGetLastError());
+  }
+  if (p.per) {   // the new priorities of the batch's episodes, from the tail's |td m| record
+    hipLaunchKernelGGL(per_priority_kernel, dim3((d.B + 3) / 4), dim3(256), 0, s, d, rp, (const float*)h->TDA,
+                       h->per.prio, h->per.prio_max, h->per.n_prio, h->per.eps);
     MQ_HIP(hipGetLastError());
   }
   return MQ_OK;
@@ -707,6 +763,7 @@ int mq_destroy(mq_handle* h) {
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->ws) (void)hipFree(h->ws);
   if (h->YT) (void)hipFree(h->YT);
+  if (h->TDA) (void)hipFree(h->TDA);
   if (h->comm && h->comm_owned) (void)ncclCommDestroy(h->comm);
   delete h;
   return MQ_OK;
@@ -743,12 +800,24 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
   if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
   if (!h->on || !h->tg || !h->grad || !h->sq || !h->stats)
     return set_err(MQ_ERR_STATE, "training needs online, target, grad, sq_avg and stats bound (mq_bind)");
+  const bool per = h->per_armed;
+  h->per_armed = false;   // armed for one step, whatever becomes of it
   int rc = check_batch(h, batch);
   if (rc) return rc;
+  if (per) {
+    if (h->comm || h->dp)
+      return set_err(MQ_ERR_ARG, "prioritized replay does not support data parallelism (a communicator is attached "
+                                 "or mq_set_data_parallel is on)");
+    if (!batch->ep_ids || batch->ep_ids_host)
+      return set_err(MQ_ERR_ARG, "a prioritized-replay step needs device episode ids (mq_replay.ep_ids, ep_ids_host "
+                                 "NULL): they are the priority slots it writes");
+    if (batch->n_episodes > h->per.n_prio)
+      return set_err(MQ_ERR_ARG, "mq_per.n_prio is smaller than the replay's n_episodes");
+  }
   Step st{h, make_dims(h, batch), make_rep(batch), make_lay(h), h->w, h->curmax_user ? h->curmax_user : h->curmax_ws,
           s, PhaseTimer{h, s}};
   // a handle with the TD(lambda) workspace runs the lambda passes: cfg.td_lambda > 0 or MQ_PLAN lambda_path=1
-  const StepPlan p = plan_step(h->cfg, h->ov, st.d, st.rp.nids > 0, h->YT != nullptr, device_cus(h));
+  const StepPlan p = plan_step(h->cfg, h->ov, st.d, st.rp.nids > 0, h->YT != nullptr, device_cus(h), per);
   st.w.rec_coef = p.rec_coef;
   if ((rc = st.forward(p)) || (rc = st.hypernet(p)) || (rc = st.mixer_tail(p)) || (rc = st.bptt(p)) ||
       (rc = st.reduce(p)))
@@ -761,6 +830,7 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
   h->plan = p.report;
   h->have_fb = true;
   h->have_lambda = p.lambda;
+  h->have_per = p.per;
   return MQ_OK;
 }
 
@@ -866,6 +936,42 @@ int mq_comm_detach(mq_handle* h) {
   return MQ_OK;
 }
 
+int mq_per_sample(const float* prio, int32_t n_live, const float* u, int32_t batch, float alpha, float beta,
+                  int64_t* ids, float* weights, void* stream) {
+  if (!prio || !u || !ids || !weights) return set_err(MQ_ERR_ARG, "NULL pointer in mq_per_sample");
+  if (!(alpha >= 0.0f)) return set_err(MQ_ERR_ARG, "per alpha must be >= 0");
+  if (!(beta >= 0.0f && beta <= 1.0f)) return set_err(MQ_ERR_ARG, "per beta must be in [0, 1]");
+  if (n_live < 1 || n_live > PER_NMAX)
+    return set_err(MQ_ERR_ARG, "mq_per_sample: n_live " + std::to_string(n_live) + " outside [1, " +
+                                   std::to_string(PER_NMAX) + "]");
+  if (batch < 1) return set_err(MQ_ERR_ARG, "mq_per_sample: batch must be >= 1");
+  static_assert(PER_NMAX == MQ_PER_MAX_LIVE && PER_THREADS == 1 << PER_SCAN_DEPTH, "per_kernels.hpp constants");
+  hipLaunchKernelGGL(per_sample_kernel, dim3(1), dim3(PER_THREADS), 0, (hipStream_t)stream, prio, (int)n_live, u,
+                     (int)batch, alpha, beta, ids, weights);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+int mq_set_per(mq_handle* h, const mq_per* per) {
+  if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
+  h->per_armed = false;
+  if (!per) return MQ_OK;
+  if (!per->weights || !per->prio || !per->prio_max) return set_err(MQ_ERR_ARG, "NULL pointer in mq_per");
+  if (!(per->eps > 0.0f)) return set_err(MQ_ERR_ARG, "per eps must be > 0");
+  if (per->n_prio < 1) return set_err(MQ_ERR_ARG, "mq_per.n_prio must be >= 1");
+  if (!h->TDA) {
+    const int64_t len = align_up((int64_t)h->cfg.max_seq * h->cfg.max_batch);
+    const hipError_t e = hipMalloc((void**)&h->TDA, len * sizeof(float));
+    if (e != hipSuccess) {
+      h->TDA = nullptr;
+      return set_err(MQ_ERR_HIP, std::string("prioritized-replay workspace hipMalloc: ") + hipGetErrorString(e));
+    }
+  }
+  h->per = *per;
+  h->per_armed = true;
+  return MQ_OK;
+}
+
 int mq_update_targets(mq_handle* h, void* stream) {
   if (!h || !h->on || !h->tg) return set_err(MQ_ERR_STATE, "mq_update_targets needs online and target bound");
   MQ_HIP(hipMemcpyAsync(h->tg, h->on, h->P * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -888,6 +994,11 @@ int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, vo
       if (!h->have_lambda) return set_err(MQ_ERR_STATE, "the last step did not run the TD(lambda) passes");
       src = which == 4 ? h->YT : h->G;
       cnt = (int64_t)d.T * d.B * (d.mixer == MQ_MIXER_NONE ? d.n : 1);
+      break;
+    case 6:
+      if (!h->have_per) return set_err(MQ_ERR_STATE, "the last step was not a prioritized-replay step");
+      src = h->TDA;
+      cnt = (int64_t)d.T * d.B;
       break;
     default: return set_err(MQ_ERR_ARG, "unknown intermediate id");
   }

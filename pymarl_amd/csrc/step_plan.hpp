@@ -126,6 +126,7 @@ struct StepPlan {
   int hyper = MQ_HYP_NONE;      // MQ_HYP_*: the hypernet kernel
   int mix = MQ_MIX_GENERIC;     // MQ_MIX_*: the mixer tail's kernel
   bool lambda = false;          // the tail runs as the TD(lambda) passes
+  bool per = false;             // prioritized replay: the loss-bearing pass in its PER form, then per_priority_kernel
   // dW_hyper (QMIX): tiles appended to the fused BPTT's grid, or fused with pass 1 of the reduction; tj x ts output
   // tiles in ns m-slices, ndwh tiles in all
   bool dwh_in_bwd = false, dwh_in_red1 = false;
@@ -138,7 +139,7 @@ struct StepPlan {
 };
 
 inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims& d, bool inline_ids,
-                          bool have_lambda_ws, int num_cu) {
+                          bool have_lambda_ws, int num_cu, bool per = false) {
   StepPlan p;
   const int64_t RT = (int64_t)d.Tp * d.R;
   const bool qmix = c.mixer == MQ_MIXER_QMIX;
@@ -190,6 +191,7 @@ inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims
   p.mix = fast && d.A <= 16 ? MQ_MIX_FAST16 : fast && d.A <= 32 ? MQ_MIX_FAST32 : stream ? MQ_MIX_STREAM
                                                                                         : MQ_MIX_GENERIC;
   p.lambda = have_lambda_ws;   // cfg.td_lambda > 0 or MQ_PLAN lambda_path=1 (mq_create)
+  p.per = per;   // armed for this step (mq_set_per): changes no other choice
   p.nblk_mix = (d.M + 3) / 4;
 
   // BPTT slabs, dW1 split
@@ -235,6 +237,7 @@ inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims
   r.dwh = p.dwh_in_bwd ? 1 : 0;
   r.td_lambda = p.lambda ? 1 : 0;
   r.bwd_lean = p.lean ? 1 : 0;
+  r.per = p.per ? 1 : 0;
   return p;
 }
 

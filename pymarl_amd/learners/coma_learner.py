@@ -40,7 +40,7 @@ from .. import _lib
 from ..modules.critics.coma import COMACritic
 from ..modules.flat import pack, rebind
 from .dp import DPCheck, SharedComm, dp_world, local_shard, native_comm_wanted, shard_bounds
-from .q_learner import replay_view
+from .q_learner import is_per_batch, replay_view
 from ..components.episode_buffer import is_replay_view
 
 CC_MAXR = 80   # coma_chain.hpp: most critic rows (B * n_agents) the persistent chain takes
@@ -198,6 +198,9 @@ class COMALearner:
     # -- reference API ---------------------------------------------------------------------------------------
     def train(self, batch, t_env: int, episode_num: int):
         _lib.require_gpu(self._agent)
+        if is_per_batch(batch):
+            raise ValueError("COMALearner is on-policy and does not take a PrioritizedReplayBuffer batch: its loss "
+                             "carries no importance weights and it writes no priorities back")
         mode = self.dp_mode(batch.batch_size)
         if mode is not None:
             rank, world = dp_world()

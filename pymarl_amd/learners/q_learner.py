@@ -27,7 +27,7 @@ import torch as th
 from torch.optim import RMSprop
 
 from .. import _lib
-from ..components.episode_buffer import is_replay_view
+from ..components.episode_buffer import PrioritizedBatch, is_replay_view
 from ..modules.flat import pack, rebind
 from .dp import DPCheck, SharedComm, allreduce_grad_buffer, dp_world, local_shard, native_comm_wanted
 from ..modules.mixers.qmix import QMixer
@@ -75,6 +75,11 @@ def make_config(args, mixer, input_dim=None, max_batch=1, max_seq=2):
     return cfg
 
 
+def is_per_batch(batch):
+    """True for a PrioritizedReplayBuffer sample: train() runs it as a prioritized-replay step."""
+    return isinstance(batch, PrioritizedBatch)
+
+
 def _field_view(t, dtype):
     """(tensor usable by the kernels, t_stride): [B][T][...] with trailing dims contiguous and the right dtype."""
     if t.dtype != dtype:
@@ -98,7 +103,13 @@ def replay_view(batch, avail_bits=True):
     if is_replay_view(batch):
         src = batch.source.data.transition_data
         tstride = batch.source.max_seq_length
-        if len(batch.ep_ids_np) <= _lib.INLINE_IDS:
+        if is_per_batch(batch):
+            # prioritized replay: the ids were written by the sampler kernel and exist on the device only
+            ids = batch.ep_ids
+            keep.append(ids)
+            rep.ep_ids = ids.data_ptr()
+            rep.ep_ids_host = None
+        elif len(batch.ep_ids_np) <= _lib.INLINE_IDS:
             # ids travel in the kernel arguments: no host-to-device copy on the step's stream
             host = np.ascontiguousarray(batch.ep_ids_np, dtype=np.int64)
             keep.append(host)
@@ -265,6 +276,10 @@ class QLearner:
         # decided per call: torch.distributed may be initialised after the handle was created; mq_apply must then
         # recompute the gradient norm from the all-reduced buffer
         dp = self._dp_active()
+        per = is_per_batch(batch)
+        if per and (self.dp or getattr(self, "force_dp_norm", False)):
+            raise ValueError("learner_dp is not supported with a PrioritizedReplayBuffer batch: the priorities and "
+                             "importance weights belong to one device's buffer")
         if dp:
             batch = self._local_batch(batch)
         h = self._get_handle(batch)
@@ -274,6 +289,13 @@ class QLearner:
             h.dp_on = want
         rep, keep = replay_view(batch, self.use_avail_bits)
         lib, s = h.lib, _lib.stream_ptr()
+        if per:
+            # weighted loss, then the new priorities into the buffer: armed for this step only (mq_set_per)
+            src = batch.source
+            pr = _lib.MQPer(weights=batch.weights.data_ptr(), prio=src.prio.data_ptr(),
+                            prio_max=src.prio_max.data_ptr(), n_prio=src.prio.numel(), eps=src.eps)
+            keep.append(batch.weights)
+            _lib.check(lib.mq_set_per(h.h, ctypes.byref(pr)))
         if dp and not h.native:
             _lib.check(lib.mq_forward_backward(h.h, ctypes.byref(rep), s))
             allreduce_grad_buffer(self._grad)
@@ -363,7 +385,8 @@ class QLearner:
     def last_plan(self):
         """Kernel variants the last train() launched (mq_last_plan): rows, fused_fwd, rw_fwd, fused_bwd, rw_bwd,
         inline_ids, hyper, mix, tiles, dwh (where QMIX's dW_hyper ran: "red1" or "bptt_grid"), td_lambda (1: the
-        mixer tail ran as the TD(lambda) passes), bwd_lean (1: the fused BPTT ran its lean per-step path)."""
+        mixer tail ran as the TD(lambda) passes), bwd_lean (1: the fused BPTT ran its lean per-step path), per (1: a
+        prioritized-replay step: weighted loss, then the priority write-back)."""
         pl = _lib.MQPlan()
         _lib.check(self._handle.lib.mq_last_plan(self._handle.h, ctypes.byref(pl)))
         d = pl.as_dict()
@@ -383,7 +406,8 @@ class QLearner:
         """0 / 1: online / target mac_out as (B, T+1, n, A); 2: dLoss_num/dchosen as (B, T, n);
         3: online relu(fc1(inputs)) as (B, T+1, n, 64). After a TD(lambda) step (last_plan()["td_lambda"] == 1):
         4: y', the target network's mixed value at step t + 1, as (B, T, 1), or (B, T, n) without a mixer;
-        5: the lambda targets in the same shape."""
+        5: the lambda targets in the same shape. After a prioritized-replay step (last_plan()["per"] == 1): 6: the
+        unweighted |td * mask| the priority write-back summed, as (B, T, 1) (no mixer: summed over the agents)."""
         B, Tp = self._last_batch
         n, A = self.args.n_agents, self.args.n_actions
         cnt = ctypes.c_int64()
@@ -395,7 +419,7 @@ class QLearner:
             return out.view(Tp, B, n, A).permute(1, 0, 2, 3)
         if which == 3:
             return out.view(Tp, B, n, -1).permute(1, 0, 2, 3)
-        if which in (4, 5):
+        if which in (4, 5, 6):
             return out.view(Tp - 1, B, -1).permute(1, 0, 2)
         return out.view(Tp - 1, B, n).permute(1, 0, 2)
 
