@@ -35,12 +35,26 @@ enum { MQ_NSUMS = 8 };   /* tail of the gradient buffer: sum (td*m)^2 (Huber: su
 enum { MQ_NSTATS = 8 };  /* loss, grad_norm, td_error_abs, q_taken_mean, target_mean, mask_sum, clip coefficient,
                            0 (reserved) */
 
-/* Parameter tensors, in the reference's parameters()/state_dict order: RNNAgent (rnn_agent.py:19-21) then
- * QMixer (qmix.py:14-23). mq_param_offsets fills offsets[MQ_P_COUNT + 1] (last = total). */
+/* Parameter tensors: RNNAgent (rnn_agent.py:19-21) then QMixer (qmix.py:14-23). mq_param_offsets fills
+ * offsets[MQ_P_COUNT + 1] (last = total) with each tensor's place in the flat buffer, which follows the modules'
+ * parameters() / state_dict order.
+ *
+ * With one hypernet layer (mq_config.hypernet_layers 0 or 1) that order is the enum's order up to MQ_P_V2_B, and
+ * MQ_P_HW1_W .. MQ_P_HWF_B are hyper_w_1.weight / .bias and hyper_w_final.weight / .bias. The four second-layer
+ * entries are absent: each reports offset = total (a tensor of zero floats at the end of the buffer).
+ *
+ * With two layers (hypernet_layers = 2) MQ_P_HW1_W / _B and MQ_P_HWF_W / _B name the state-fed FIRST layers
+ * (hyper_w_1.0, hyper_w_final.0: [hypernet_embed][state_dim] and [hypernet_embed]) and MQ_P_HW1_W2 / _B2,
+ * MQ_P_HWF_W2 / _B2 the second layers (hyper_w_1.2: [embed * n_agents][hypernet_embed]; hyper_w_final.2:
+ * [embed][hypernet_embed]). The buffer's order is upstream PyMARL's parameters() order
+ *   ... fc2.bias, hyper_w_1.0.weight, hyper_w_1.0.bias, hyper_w_1.2.weight, hyper_w_1.2.bias, hyper_w_final.0.weight,
+ *   hyper_w_final.0.bias, hyper_w_final.2.weight, hyper_w_final.2.bias, hyper_b_1.weight, ... V.2.bias
+ * so the offsets are NOT monotone in the enum index: never derive a tensor's size from the next enum entry's
+ * offset. The new entries sit after MQ_P_V2_B so that every earlier entry keeps its number. */
 enum {
   MQ_P_FC1_W, MQ_P_FC1_B, MQ_P_RNN_W_IH, MQ_P_RNN_W_HH, MQ_P_RNN_B_IH, MQ_P_RNN_B_HH, MQ_P_FC2_W, MQ_P_FC2_B,
   MQ_P_HW1_W, MQ_P_HW1_B, MQ_P_HWF_W, MQ_P_HWF_B, MQ_P_HB1_W, MQ_P_HB1_B, MQ_P_V0_W, MQ_P_V0_B, MQ_P_V2_W,
-  MQ_P_V2_B, MQ_P_COUNT
+  MQ_P_V2_B, MQ_P_HW1_W2, MQ_P_HW1_B2, MQ_P_HWF_W2, MQ_P_HWF_B2, MQ_P_COUNT
 };
 
 typedef struct mq_config {
@@ -62,7 +76,14 @@ typedef struct mq_config {
                                 scan over t, loss + mixer backward). Outside [0, 1] or NaN: MQ_ERR_ARG; so is a
                                 max_seq whose scan inputs, (max_seq - 1) * (k + 3) floats with k = 1 (no mixer:
                                 n_agents), pass 64 KB of LDS. */
+  int32_t hypernet_layers;   /* QMIX: 0 or 1 = hyper_w_1 / hyper_w_final are one Linear each (the reference; every
+                                kernel of that path runs as it always did); 2 = Linear(S, hypernet_embed) -> ReLU ->
+                                Linear(hypernet_embed, .), upstream PyMARL's two-layer hypernetwork. Anything else:
+                                MQ_ERR_ARG. Ignored without a QMIX mixer. */
+  int32_t hypernet_embed;    /* width of the two-layer hypernet's hidden layer, 1 .. MQ_HYPERNET_EMBED_MAX (two layers
+                                only; outside: MQ_ERR_ARG) */
 } mq_config;
+enum { MQ_HYPERNET_EMBED_MAX = 64 };
 
 /* A batch of episodes as the learner reads it: the replay storage (reference scheme dtypes, episode-major
  * [episode][t][...], run.py:122-135) plus the sampled episode ids. t_len = max_t_filled() of the batch
@@ -166,7 +187,9 @@ int mq_set_per(mq_handle* h, const mq_per* per);
  * network's mixed value at step t + 1, as [t][b] (no mixer: [t][b*n+a], one value per agent), t < t_len - 1;
  * 5 = the lambda targets in the same layout.
  * After a prioritized-replay step (mq_plan.per = 1; MQ_ERR_STATE otherwise): 6 = |td * mask| of every transition,
- * unweighted, as [t][b] (no mixer: summed over the agents), t < t_len - 1: what the priority write-back summed. */
+ * unweighted, as [t][b] (no mixer: summed over the agents), t < t_len - 1: what the priority write-back summed.
+ * After a step of the two-layer hypernet (mq_last_hyper_layers = 2; MQ_ERR_STATE otherwise): 7 = the online net's
+ * first-layer pre-activations [hyper_w_1.0 | hyper_w_final.0] as [t][b][2 * hypernet_embed], t < t_len - 1. */
 int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, void* stream);
 
 /* BasicMAC.forward(ep_batch, t) for every episode of `batch`: h_in/h_out [batch*n][64] (h_in may equal
@@ -185,6 +208,11 @@ int mq_greedy_actions(const float* q, const int32_t* avail, int64_t* out, int32_
  * [rows][state_dim], q_tot [rows]. */
 int mq_qmix_forward(const float* mixer, int32_t n_agents, int32_t state_dim, int32_t embed_dim,
                     const float* agent_qs, const float* states, float* q_tot, int32_t rows, void* stream);
+/* The same for a two-layer QMixer (hypernet_layers = 2): mixer = its parameters in parameters() order
+ * (hyper_w_1.0.weight .. V.2.bias, see MQ_P_*), hypernet_embed in 1 .. MQ_HYPERNET_EMBED_MAX. */
+int mq_qmix_forward2(const float* mixer, int32_t n_agents, int32_t state_dim, int32_t embed_dim,
+                     int32_t hypernet_embed, const float* agent_qs, const float* states, float* q_tot, int32_t rows,
+                     void* stream);
 
 /* Which kernel variants the last mq_forward_backward launched (test / profiling introspection; no device sync).
  * rw_fwd / rw_bwd: rows per workgroup of the unfused recurrences (0 when the fused kernel ran). */
@@ -212,6 +240,12 @@ typedef struct mq_plan {
                             and the priority write-back followed it */
 } mq_plan;
 int mq_last_plan(const mq_handle* h, mq_plan* out);
+/* The hypernet of the last mq_forward_backward, the plan item `hyper_layers`. mq_plan itself keeps its size and `per`
+ * as its last field (hosts built against it stay valid), so the item has an entry of its own. 2: the two-layer QMIX
+ * hypernet ran, as launches of its own around the mixer tail (layer 1, layer 2 forward; layer 2 backward, weight
+ * gradients); mq_plan.hyper then names layer 1's kernel and mq_plan.dwh is 0. 1: the one-layer hypernet. 0: no QMIX
+ * mixer. -1: NULL handle, or no forward/backward has run. */
+int32_t mq_last_hyper_layers(const mq_handle* h);
 
 /* Optional per-kernel HIP-event timing of train steps (bench / profiling): events bracket every phase whose bit
  * is set in phase_mask (bit i = phase i of mq_phase_names), in a ring of `slots` steps; slots = 0 turns it off. */

@@ -18,6 +18,8 @@ PARAM_NAMES = [
     "fc1.weight", "fc1.bias", "rnn.weight_ih", "rnn.weight_hh", "rnn.bias_ih", "rnn.bias_hh", "fc2.weight",
     "fc2.bias", "hyper_w_1.weight", "hyper_w_1.bias", "hyper_w_final.weight", "hyper_w_final.bias",
     "hyper_b_1.weight", "hyper_b_1.bias", "V.0.weight", "V.0.bias", "V.2.weight", "V.2.bias",
+    # two-layer hypernet only (hypernet_layers: 2): the entries above then name hyper_w_1.0 / hyper_w_final.0
+    "hyper_w_1.2.weight", "hyper_w_1.2.bias", "hyper_w_final.2.weight", "hyper_w_final.2.bias",
 ]
 P_COUNT = len(PARAM_NAMES)
 
@@ -26,7 +28,7 @@ EXPORTS = [
     "mq_last_error", "mq_create", "mq_destroy", "mq_param_offsets", "mq_bind", "mq_forward_backward", "mq_apply",
     "mq_train_step", "mq_update_targets", "mq_copy_intermediate", "mq_mac_forward", "mq_agent_forward",
     "mq_greedy_actions", "mq_set_timing", "mq_phase_times", "mq_phase_names", "mq_set_data_parallel",
-    "mq_last_plan", "mq_qmix_forward", "mq_per_sample", "mq_set_per",
+    "mq_last_plan", "mq_qmix_forward", "mq_qmix_forward2", "mq_last_hyper_layers", "mq_per_sample", "mq_set_per",
     # include/mc_coma.h
     "mc_create", "mc_destroy", "mc_param_offsets", "mc_bind", "mc_train_step", "mc_update_targets", "mc_policy",
     "mc_copy_intermediate", "mc_set_timing", "mc_phase_times", "mc_last_critic_path", "mq_comm_unique_id", "mq_comm_attach",
@@ -53,8 +55,11 @@ class MQConfig(ctypes.Structure):
         ("obs_agent_id", ctypes.c_int32), ("gamma", ctypes.c_float), ("lr", ctypes.c_float),
         ("optim_alpha", ctypes.c_float), ("optim_eps", ctypes.c_float), ("grad_norm_clip", ctypes.c_float),
         ("max_batch", ctypes.c_int32), ("max_seq", ctypes.c_int32), ("huber_delta", ctypes.c_float),
-        ("td_lambda", ctypes.c_float),
+        ("td_lambda", ctypes.c_float), ("hypernet_layers", ctypes.c_int32), ("hypernet_embed", ctypes.c_int32),
     ]
+
+
+HYPERNET_EMBED_MAX = 64   # MQ_HYPERNET_EMBED_MAX
 
 
 class MQReplay(ctypes.Structure):
@@ -140,6 +145,8 @@ def load(required=True):
         "mq_set_data_parallel": ([vp, i32], ctypes.c_int),
         "mq_last_plan": ([vp, ctypes.POINTER(MQPlan)], ctypes.c_int),
         "mq_qmix_forward": ([vp, i32, i32, i32, vp, vp, vp, i32, vp], ctypes.c_int),
+        "mq_last_hyper_layers": ([vp], i32),
+        "mq_qmix_forward2": ([vp, i32, i32, i32, i32, vp, vp, vp, i32, vp], ctypes.c_int),
         "mq_per_sample": ([vp, i32, vp, i32, ctypes.c_float, ctypes.c_float, vp, vp, vp], ctypes.c_int),
         "mq_set_per": ([vp, ctypes.POINTER(MQPer)], ctypes.c_int),
         "mc_critic_forward_workspace": ([ctypes.POINTER(MCConfig), i32, i32], i64),

@@ -86,7 +86,7 @@ MQ_DEV void hyper_fwd_body(const Dims& d, const Rep& rp, const float* __restrict
     // ---- loader waves (hyper_ws_kernel's fetch / stage)
     const int lw = wv;
     const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)P, (short)0, (int)(L.o[MQ_P_COUNT] * sizeof(float)), 0x00020000);
+        (void*)P, (short)0, (int)(L.o[LAY_N] * sizeof(float)), 0x00020000);
     const int voff = 4 * lane;
     float wr[48];
     auto fetch = [&](int c) {

@@ -215,7 +215,7 @@ __global__ __launch_bounds__(HYWS_THREADS) void hyper_ws_kernel(Dims d, Rep rp, 
     // ---- loader waves
     const int lw = wv;
     const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)P, (short)0, (int)(L.o[MQ_P_COUNT] * sizeof(float)), 0x00020000);
+        (void*)P, (short)0, (int)(L.o[LAY_N] * sizeof(float)), 0x00020000);
     const int voff = 4 * lane;
     uint64_t* stl = (uint64_t*)S0 + 32 * (blockIdx.y * gridDim.x + blockIdx.x) + 16;
     const bool stamp = (VAR & 1) && lw == 0 && lane == 0;

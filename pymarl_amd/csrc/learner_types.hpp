@@ -49,8 +49,12 @@ struct Rep {
   MQ_DEV int64_t ep(int b) const { return nids ? (int64_t)ids[b] : (ep_ids ? ep_ids[b] : (int64_t)b); }
 };
 
+// The offsets every kernel of the step carries: the tensors up to V.2.bias, then the buffer's total. The two-layer
+// hypernet's second-layer tensors (MQ_P_HW1_W2 ..) are not in it: only the hyper2_kernels.hpp launches read them, from
+// their own Hyp2Lay, and the kernels of the one-layer step keep their argument blocks.
+constexpr int LAY_N = MQ_P_V2_B + 1;
 struct Lay {
-  int64_t o[MQ_P_COUNT + 1];
+  int64_t o[LAY_N + 1];
 };
 
 // Activation workspace, time-major: row index tr = t*R + r with r = b*n + agent.

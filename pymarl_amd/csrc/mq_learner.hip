@@ -6,6 +6,8 @@
 //   gru_fwd  recur h_t = GRU(GI_t, h_{t-1})                              both nets, serial over T
 //   fc2      gemm  Q = W2 H + b2                                          both nets
 //   hyper    gemm  QMIX hypernet outputs of state[:, :-1] / state[:, 1:] both nets (QMIX only)
+//            (two-layer hypernet, mq_config.hypernet_layers = 2: layer 1 and layer 2 as two launches here, layer 2's
+//            backward and the hypernet's weight gradients as two more in `dwh`, hyper2_kernels.hpp)
 //   mix      per (t, episode): chosen gather, double-Q select, mixer fwd, TD, masked L2 sums, mixer bwd
 //            (TD(lambda) targets, mq_config.td_lambda > 0: three launches, td_lambda_kernel.hpp)
 //            (prioritized replay, mq_set_per: the loss-bearing pass in its PER form, then per_priority_kernel;
@@ -36,6 +38,7 @@
 #include "td_lambda_kernel.hpp"
 #include "per_kernels.hpp"
 #include "hyper_kernel.hpp"
+#include "hyper2_kernels.hpp"
 #include "dwh_kernel.hpp"
 #include "optim_kernels.hpp"
 #include "module_fwd.hpp"
@@ -145,6 +148,13 @@ struct mq_handle {
   bool per_armed = false;
   float* TDA = nullptr;
   bool have_per = false;   // the last step was a PER step (mq_copy_intermediate 6)
+  // the two-layer hypernet (cfg.hypernet_layers = 2): its layout, and the layer-1 tensors A1 [2][max M][N1] and dA1
+  // [max M][N1], allocated only for such a handle
+  bool hyper2 = false;
+  Hyp2Lay y2{};
+  float *A1 = nullptr, *dA1 = nullptr;
+  bool have_h2 = false;   // the last step ran it (mq_copy_intermediate 7)
+  int hyper_layers = 0;   // of the last step (mq_last_hyper_layers)
   int num_cu = 0;
   // timing: a ring of `slots` steps x PH_N (start, stop) event pairs; phases outside `mask` are not recorded
   int slots = 0;
@@ -164,17 +174,42 @@ void compute_layout(mq_handle* h) {
   sz[MQ_P_RNN_W_IH] = 3LL * Hd * Hd; sz[MQ_P_RNN_W_HH] = 3LL * Hd * Hd;
   sz[MQ_P_RNN_B_IH] = 3 * Hd; sz[MQ_P_RNN_B_HH] = 3 * Hd;
   sz[MQ_P_FC2_W] = (int64_t)A * Hd; sz[MQ_P_FC2_B] = A;
+  // the buffer's order: the enum's, with the two-layer hypernet's second layers behind their first layers
+  // (parameters() order of upstream's QMixer); at one layer the second-layer entries are empty and come last
+  int order[MQ_P_COUNT];
+  int no = 0;
+  for (int i = 0; i <= MQ_P_V2_B; ++i) {
+    order[no++] = i;
+    if (h->hyper2 && i == MQ_P_HW1_B) { order[no++] = MQ_P_HW1_W2; order[no++] = MQ_P_HW1_B2; }
+    if (h->hyper2 && i == MQ_P_HWF_B) { order[no++] = MQ_P_HWF_W2; order[no++] = MQ_P_HWF_B2; }
+  }
+  if (!h->hyper2)
+    for (int i = MQ_P_HW1_W2; i < MQ_P_COUNT; ++i) order[no++] = i;
   if (c.mixer == MQ_MIXER_QMIX) {
     sz[MQ_P_HW1_W] = (int64_t)E * n * S; sz[MQ_P_HW1_B] = (int64_t)E * n;
     sz[MQ_P_HWF_W] = (int64_t)E * S; sz[MQ_P_HWF_B] = E;
+    if (h->hyper2) {
+      const int64_t He = c.hypernet_embed;
+      sz[MQ_P_HW1_W] = He * S; sz[MQ_P_HW1_B] = He;
+      sz[MQ_P_HWF_W] = He * S; sz[MQ_P_HWF_B] = He;
+      sz[MQ_P_HW1_W2] = (int64_t)E * n * He; sz[MQ_P_HW1_B2] = (int64_t)E * n;
+      sz[MQ_P_HWF_W2] = (int64_t)E * He; sz[MQ_P_HWF_B2] = E;
+    }
     sz[MQ_P_HB1_W] = (int64_t)E * S; sz[MQ_P_HB1_B] = E;
     sz[MQ_P_V0_W] = (int64_t)E * S; sz[MQ_P_V0_B] = E;
     sz[MQ_P_V2_W] = E; sz[MQ_P_V2_B] = 1;
   }
   int64_t o = 0;
-  for (int i = 0; i < MQ_P_COUNT; ++i) { h->off[i] = o; o += sz[i]; }
+  for (int i = 0; i < MQ_P_COUNT; ++i) { h->off[order[i]] = o; o += sz[order[i]]; }
   h->off[MQ_P_COUNT] = o;
   h->P = o;
+  if (h->hyper2) {
+    Hyp2Lay& y = h->y2;
+    y.w1a = h->off[MQ_P_HW1_W]; y.b1a = h->off[MQ_P_HW1_B]; y.w12 = h->off[MQ_P_HW1_W2]; y.b12 = h->off[MQ_P_HW1_B2];
+    y.wfa = h->off[MQ_P_HWF_W]; y.bfa = h->off[MQ_P_HWF_B]; y.wf2 = h->off[MQ_P_HWF_W2]; y.bf2 = h->off[MQ_P_HWF_B2];
+    y.hbw = h->off[MQ_P_HB1_W]; y.hbb = h->off[MQ_P_HB1_B]; y.v0w = h->off[MQ_P_V0_W]; y.v0b = h->off[MQ_P_V0_B];
+    y.He = c.hypernet_embed; y.E = E; y.nE = n * E; y.N1 = 2 * y.He + 2 * E;
+  }
   h->len_rnn = h->off[MQ_P_FC2_B] + A - h->off[MQ_P_RNN_W_IH];
   h->pitch_rnn = (h->len_rnn + 3) & ~int64_t(3);
   h->len_mix = h->off[MQ_P_V2_W] - h->off[MQ_P_HW1_W];
@@ -200,7 +235,8 @@ Rep make_rep(const mq_replay* b) {
 
 Lay make_lay(const mq_handle* h) {
   Lay L;
-  for (int i = 0; i <= MQ_P_COUNT; ++i) L.o[i] = h->off[i];
+  for (int i = 0; i < LAY_N; ++i) L.o[i] = h->off[i];
+  L.o[LAY_N] = h->P;
   return L;
 }
 
@@ -415,6 +451,7 @@ struct Step {
   int forward(const StepPlan& p);
   int hypernet(const StepPlan& p);
   int mixer_tail(const StepPlan& p);
+  int hypernet2_backward(const StepPlan& p);
   int bptt(const StepPlan& p);
   int reduce(const StepPlan& p);
 };
@@ -486,6 +523,15 @@ int Step::forward(const StepPlan& p) {
 int Step::hypernet(const StepPlan& p) {
   if (p.hyp_place != HYP_OWN_LAUNCH) return MQ_OK;
   pt.begin(PH_HYP);
+  if (p.hyper2) {
+    // layer 1 (pre-activations A1, and S0), then layer 2 into HYP: both nets each (hyper2_kernels.hpp)
+    const Hyp2Lay& y = h->y2;
+    Hyp1Prob p1{d, rp, y, h->on, h->tg, h->A1, w.S0};
+    MQ_HIP(launch_gemm(p1, d.M, y.N1, 2, s));
+    Hyp2FwdProb p2{y, h->on, h->tg, h->A1, w.HYP, d.M, d.NH};
+    MQ_HIP(launch_gemm(p2, d.M, d.NH, 2, s));
+    return MQ_OK;
+  }
   if (p.hyper == MQ_HYP_WS) {
     // wave-specialised weight streaming (hyper_kernel.hpp)
     MQ_LDS(hyper_ws_kernel<0>, hyper_ws_lds_bytes(d.S));
@@ -533,6 +579,20 @@ int Step::mixer_tail(const StepPlan& p) {
                        h->per.prio, h->per.prio_max, h->per.n_prio, h->per.eps);
     MQ_HIP(hipGetLastError());
   }
+  return MQ_OK;
+}
+
+// The two-layer hypernet behind the mixer tail's dHYP: layer 2's backward into dA1, then every hypernet weight and
+// bias gradient as p.ns m-slices of slab_mix (reduce() sums them).
+int Step::hypernet2_backward(const StepPlan& p) {
+  if (!p.hyper2) return MQ_OK;
+  pt.begin(PH_DWH);
+  const Hyp2Lay& y = h->y2;
+  Hyp2BwdProb pb{y, h->on, h->A1, w.dHYP, h->dA1, d.M, d.NH};
+  MQ_HIP(launch_gemm(pb, d.M, y.N1, 1, s));
+  const int t0 = (y.nE + GBM - 1) / GBM, t1 = (y.E + GBM - 1) / GBM, t2 = (y.N1 + GBM - 1) / GBM;
+  Hyp2DwProb pw{y, h->A1, h->dA1, w.dHYP, w.S0, w.slab_mix, h->len_mix, h->off[MQ_P_HW1_W], d.M, d.NH, d.S, p.ns, t0, t1};
+  MQ_HIP(launch_gemm(pw, (t0 + t1 + t2) * GBM, std::max(y.He, d.S), p.ns, s));
   return MQ_OK;
 }
 
@@ -667,6 +727,11 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
   if (c.obs_dim < 1 || c.state_dim < 1) return set_err(MQ_ERR_ARG, "obs_dim / state_dim must be positive");
   if (c.mixer == MQ_MIXER_QMIX && (c.mixing_embed_dim < 1 || c.mixing_embed_dim > 64))
     return set_err(MQ_ERR_ARG, "mixing_embed_dim must be in [1, 64]");
+  if (c.mixer == MQ_MIXER_QMIX && (c.hypernet_layers < 0 || c.hypernet_layers > 2))
+    return set_err(MQ_ERR_ARG, "hypernet_layers must be 1 or 2 (0: 1)");
+  const bool hyper2 = c.mixer == MQ_MIXER_QMIX && c.hypernet_layers == 2;
+  if (hyper2 && (c.hypernet_embed < 1 || c.hypernet_embed > MQ_HYPERNET_EMBED_MAX))
+    return set_err(MQ_ERR_ARG, "hypernet_embed must be in [1, " + std::to_string((int)MQ_HYPERNET_EMBED_MAX) + "]");
   if (c.max_batch < 1 || c.max_seq < 2) return set_err(MQ_ERR_ARG, "max_batch >= 1 and max_seq >= 2 required");
   if (!(c.huber_delta >= 0.0f)) return set_err(MQ_ERR_ARG, "huber_delta must be >= 0 (0: the reference's L2 loss)");
   if (!(c.td_lambda >= 0.0f && c.td_lambda <= 1.0f))
@@ -682,6 +747,7 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
   mq_handle* h = new mq_handle();
   h->cfg = c;
   h->ov = ov;
+  h->hyper2 = hyper2;
   const Dims dmax = mq::make_dims(c, c.max_batch, c.max_seq, c.max_seq);   // E, I, NH as every step derives them
   h->E = dmax.E; h->I = dmax.I; h->NH = dmax.NH;
   compute_layout(h);
@@ -750,6 +816,17 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
     }
     h->G = h->YT + len;
   }
+  if (hyper2) {
+    const int64_t len = align_up(Mm * h->y2.N1);
+    e = hipMalloc((void**)&h->A1, 3 * len * sizeof(float));
+    if (e != hipSuccess) {
+      (void)hipFree(h->ws);
+      if (h->YT) (void)hipFree(h->YT);
+      delete h;
+      return set_err(MQ_ERR_HIP, std::string("two-layer hypernet workspace hipMalloc: ") + hipGetErrorString(e));
+    }
+    h->dA1 = h->A1 + 2 * len;
+  }
   *out = h;
   return MQ_OK;
 }
@@ -764,6 +841,7 @@ int mq_destroy(mq_handle* h) {
   if (h->ws) (void)hipFree(h->ws);
   if (h->YT) (void)hipFree(h->YT);
   if (h->TDA) (void)hipFree(h->TDA);
+  if (h->A1) (void)hipFree(h->A1);
   if (h->comm && h->comm_owned) (void)ncclCommDestroy(h->comm);
   delete h;
   return MQ_OK;
@@ -817,9 +895,11 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
   Step st{h, make_dims(h, batch), make_rep(batch), make_lay(h), h->w, h->curmax_user ? h->curmax_user : h->curmax_ws,
           s, PhaseTimer{h, s}};
   // a handle with the TD(lambda) workspace runs the lambda passes: cfg.td_lambda > 0 or MQ_PLAN lambda_path=1
-  const StepPlan p = plan_step(h->cfg, h->ov, st.d, st.rp.nids > 0, h->YT != nullptr, device_cus(h), per);
+  const StepPlan p = plan_step(h->cfg, h->ov, st.d, st.rp.nids > 0, h->YT != nullptr, device_cus(h), per,
+                                 h->hyper2 ? 2 : 1);
   st.w.rec_coef = p.rec_coef;
-  if ((rc = st.forward(p)) || (rc = st.hypernet(p)) || (rc = st.mixer_tail(p)) || (rc = st.bptt(p)) ||
+  if ((rc = st.forward(p)) || (rc = st.hypernet(p)) || (rc = st.mixer_tail(p)) || (rc = st.hypernet2_backward(p)) ||
+      (rc = st.bptt(p)) ||
       (rc = st.reduce(p)))
     return rc;
   if (h->comm) {   // native data parallelism: the whole [grads | sums] buffer, summed over the ranks in stream order
@@ -831,6 +911,8 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
   h->have_fb = true;
   h->have_lambda = p.lambda;
   h->have_per = p.per;
+  h->have_h2 = p.hyper2;
+  h->hyper_layers = p.hyper_layers;
   return MQ_OK;
 }
 
@@ -862,6 +944,8 @@ int mq_last_plan(const mq_handle* h, mq_plan* out) {
   *out = h->plan;
   return MQ_OK;
 }
+
+int32_t mq_last_hyper_layers(const mq_handle* h) { return h && h->have_fb ? h->hyper_layers : -1; }
 
 int mq_set_data_parallel(mq_handle* h, int32_t on) {
   if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
@@ -1000,6 +1084,15 @@ int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, vo
       src = h->TDA;
       cnt = (int64_t)d.T * d.B;
       break;
+    case 7: {   // the online net's first 2 He columns of A1's rows (row pitch N1)
+      if (!h->have_h2) return set_err(MQ_ERR_STATE, "the last step did not run the two-layer hypernet");
+      const int64_t wd = 2 * h->y2.He;
+      if (count) *count = (int64_t)d.M * wd;
+      if (dst)
+        MQ_HIP(hipMemcpy2DAsync(dst, wd * sizeof(float), h->A1, h->y2.N1 * sizeof(float), wd * sizeof(float), d.M,
+                                hipMemcpyDeviceToDevice, (hipStream_t)stream));
+      return MQ_OK;
+    }
     default: return set_err(MQ_ERR_ARG, "unknown intermediate id");
   }
   if (count) *count = cnt;
@@ -1068,6 +1161,33 @@ int mq_qmix_forward(const float* mixer, int32_t n_agents, int32_t state_dim, int
   hipLaunchKernelGGL(qmix_forward_kernel, dim3((rows + QMF_ROWS - 1) / QMF_ROWS), dim3(256), lds,
                      (hipStream_t)stream, mixer, (int)n_agents, (int)state_dim, (int)embed_dim, agent_qs, states,
                      q_tot, (int)rows);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+int mq_qmix_forward2(const float* mixer, int32_t n_agents, int32_t state_dim, int32_t embed_dim,
+                     int32_t hypernet_embed, const float* agent_qs, const float* states, float* q_tot, int32_t rows,
+                     void* stream) {
+  if (!mixer || !agent_qs || !states || !q_tot || rows < 0) return set_err(MQ_ERR_ARG, "bad mq_qmix_forward2 args");
+  if (n_agents < 1 || n_agents > 64 || embed_dim < 1 || embed_dim > 64 || state_dim < 1)
+    return set_err(MQ_ERR_ARG, "mq_qmix_forward2: n_agents / embed_dim in [1, 64], state_dim >= 1");
+  if (hypernet_embed < 1 || hypernet_embed > MQ_HYPERNET_EMBED_MAX)
+    return set_err(MQ_ERR_ARG, "mq_qmix_forward2: hypernet_embed must be in [1, " +
+                                   std::to_string((int)MQ_HYPERNET_EMBED_MAX) + "]");
+  if (rows == 0) return MQ_OK;
+  const size_t lds = qmix_forward2_lds(n_agents, state_dim, embed_dim, hypernet_embed);
+  if (lds > 64 * 1024) return set_err(MQ_ERR_ARG, "mq_qmix_forward2: state_dim too large for the LDS staging");
+  const int64_t S = state_dim, E = embed_dim, He = hypernet_embed, nE = (int64_t)n_agents * E;
+  Qmix2Off o;
+  Hyp2Lay& y = o.Y;   // parameters() order, relative to hyper_w_1.0.weight
+  y.w1a = 0; y.b1a = He * S; y.w12 = y.b1a + He; y.b12 = y.w12 + nE * He;
+  y.wfa = y.b12 + nE; y.bfa = y.wfa + He * S; y.wf2 = y.bfa + He; y.bf2 = y.wf2 + E * He;
+  y.hbw = y.bf2 + E; y.hbb = y.hbw + E * S; y.v0w = y.hbb + E; y.v0b = y.v0w + E * S;
+  o.v2w = y.v0b + E; o.v2b = o.v2w + E;
+  y.He = (int)He; y.E = (int)E; y.nE = (int)nE; y.N1 = (int)(2 * He + 2 * E);
+  hipLaunchKernelGGL(qmix_forward2_kernel, dim3((rows + QMF2_ROWS - 1) / QMF2_ROWS), dim3(256), lds,
+                     (hipStream_t)stream, mixer, o, (int)n_agents, (int)state_dim, agent_qs, states, q_tot,
+                     (int)rows);
   MQ_HIP(hipGetLastError());
   return MQ_OK;
 }

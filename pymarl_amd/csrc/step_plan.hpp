@@ -131,6 +131,10 @@ struct StepPlan {
   // tiles in ns m-slices, ndwh tiles in all
   bool dwh_in_bwd = false, dwh_in_red1 = false;
   int tj = 0, ts = 0, ns = 0, ndwh = 0;
+  // QMIX with the two-layer hypernet (hyper2_kernels.hpp): layer 1 and layer 2 forward as launches of their own
+  // before the mixer tail, layer 2 backward and the weight gradients (ns m-slices into slab_mix) after it
+  bool hyper2 = false;
+  int hyper_layers = 0;   // what mq_last_hyper_layers returns: 2 (hyper2), 1 (the one-layer hypernet), 0 (no QMIX mixer)
   int dw1_ns = 1;     // split-K slices of the dW1 GEMM (unfused BPTT)
   int nblk_mix = 1;   // the mixer tail's workgroups: slab_v2 / loss_part slabs
   int nblk_bwd = 1;   // the BPTT's workgroups: slab_rnn slabs
@@ -139,10 +143,13 @@ struct StepPlan {
 };
 
 inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims& d, bool inline_ids,
-                          bool have_lambda_ws, int num_cu, bool per = false) {
+                          bool have_lambda_ws, int num_cu, bool per = false, int hyper_layers = 1) {
   StepPlan p;
   const int64_t RT = (int64_t)d.Tp * d.R;
   const bool qmix = c.mixer == MQ_MIXER_QMIX;
+  // the two-layer hypernet never rides in a forward or in the BPTT's grid: the forward and BPTT choices below are then
+  // those of a step without a hypernet (the same shape's VDN plan)
+  const bool hyper2 = qmix && hyper_layers == 2;
   // num_cu <= 0: the device query failed, so no pair forward and no second-wave appends
   const bool two_waves = num_cu > 0 && d.R > num_cu;   // 2R row-nets at two per CU; a second wave of BPTT rows
 
@@ -153,7 +160,7 @@ inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims
   const bool tiles = tiles_ok(d.I, d.O, d.A, d.n, d.Tp, RT) && !o.unfused_fwd && !o.unfused_bwd &&
                      (o.row_tiles == 1 || (o.row_tiles < 0 && d.R > 512));
   p.fused_bwd = !tiles && d.R <= kFusedBwdRmax && fused_bwd_ok(d.I, d.O, d.A, d.n, RT) && !o.unfused_bwd;
-  const bool hyf = qmix && hyper_ws_ok(d.S, d.E, d.NH, d.M) && hyf_ok(d.S, d.E, d.NH, d.M);   // may ride in a forward
+  const bool hyf = qmix && !hyper2 && hyper_ws_ok(d.S, d.E, d.NH, d.M) && hyf_ok(d.S, d.E, d.NH, d.M);   // may ride in a forward
   if (tiles) {
     p.fwd = FWD_TILES;
   } else if (p.rw_fwd == 1 && fused_fwd_ok(d.I, d.O, d.A, d.n, RT) && !o.unfused_fwd) {
@@ -181,7 +188,9 @@ inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims
   // hypernet kernel
   if (qmix) {
     if (p.hyp_place == HYP_ABSENT) p.hyp_place = HYP_OWN_LAUNCH;
-    p.hyper = p.hyp_place != HYP_OWN_LAUNCH || hyper_ws_ok(d.S, d.E, d.NH, d.M) ? MQ_HYP_WS   // weight streaming
+    p.hyper2 = hyper2;
+    p.hyper = hyper2 ? MQ_HYP_GEMM   // layer 1 is the state-fed GEMM at every shape
+              : p.hyp_place != HYP_OWN_LAUNCH || hyper_ws_ok(d.S, d.E, d.NH, d.M) ? MQ_HYP_WS   // weight streaming
               : hyper_ok(d.S, d.NH) ? MQ_HYP_LDS : MQ_HYP_GEMM;
   }
 
@@ -214,7 +223,10 @@ inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims
   // on the BPTT's chain waves in the kernel's tail, idle while the producers reduce the last chunk, made the BPTT 14 us
   // longer against the 8.6 us they took out of the reduction's launch: four waves per CU leave each tile's load round
   // trips exposed. Removed.)
-  if (qmix) {
+  if (hyper2) {
+    // the weight gradients are a launch of their own: m-slices into slab_mix, summed by both reduction passes
+    p.ns = p.nsplit_mix = std::max(1, std::min({o.dwh_split, kRedZ, (d.M + 1) / 2}));
+  } else if (qmix) {
     p.dwh_in_bwd = p.fused_bwd && (o.dwh_in_bwd >= 0 ? o.dwh_in_bwd != 0 : two_waves);
     p.dwh_in_red1 = !p.dwh_in_bwd;
     p.tj = (d.NH + DWH_T - 1) / DWH_T;
@@ -238,6 +250,7 @@ inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims
   r.td_lambda = p.lambda ? 1 : 0;
   r.bwd_lean = p.lean ? 1 : 0;
   r.per = p.per ? 1 : 0;
+  p.hyper_layers = hyper2 ? 2 : qmix ? 1 : 0;
   return p;
 }
 

@@ -30,7 +30,7 @@ from .. import _lib
 from ..components.episode_buffer import PrioritizedBatch, is_replay_view
 from ..modules.flat import pack, rebind
 from .dp import DPCheck, SharedComm, allreduce_grad_buffer, dp_world, local_shard, native_comm_wanted
-from ..modules.mixers.qmix import QMixer
+from ..modules.mixers.qmix import QMixer, hypernet_config
 from ..modules.mixers.vdn import VDNMixer
 
 MIXER_IDS = {None: _lib.MIXER_NONE, "vdn": _lib.MIXER_VDN, "qmix": _lib.MIXER_QMIX}
@@ -72,6 +72,9 @@ def make_config(args, mixer, input_dim=None, max_batch=1, max_seq=2):
     if q_targets not in Q_TARGETS:
         raise ValueError("q_targets {} not recognised (one of {}).".format(q_targets, ", ".join(Q_TARGETS)))
     cfg.td_lambda = float(args.td_lambda) if q_targets == "td_lambda" else 0.0
+    # upstream PyMARL's two-layer QMIX hypernetwork (hypernet_layers: 2, hypernet_embed); VDN / IQL ignore the keys
+    if mixer == _lib.MIXER_QMIX:
+        cfg.hypernet_layers, cfg.hypernet_embed = hypernet_config(args)
     return cfg
 
 
@@ -386,10 +389,12 @@ class QLearner:
         """Kernel variants the last train() launched (mq_last_plan): rows, fused_fwd, rw_fwd, fused_bwd, rw_bwd,
         inline_ids, hyper, mix, tiles, dwh (where QMIX's dW_hyper ran: "red1" or "bptt_grid"), td_lambda (1: the
         mixer tail ran as the TD(lambda) passes), bwd_lean (1: the fused BPTT ran its lean per-step path), per (1: a
-        prioritized-replay step: weighted loss, then the priority write-back)."""
+        prioritized-replay step: weighted loss, then the priority write-back), hyper_layers (2: the two-layer QMIX
+        hypernet ran as launches of its own, 1: the one-layer hypernet, 0: no QMIX mixer)."""
         pl = _lib.MQPlan()
         _lib.check(self._handle.lib.mq_last_plan(self._handle.h, ctypes.byref(pl)))
         d = pl.as_dict()
+        d["hyper_layers"] = int(self._handle.lib.mq_last_hyper_layers(self._handle.h))   # an entry of its own
         d["hyper"] = _lib.HYP_NAMES[d["hyper"]]
         d["mix"] = _lib.MIX_NAMES[d["mix"]]
         d["dwh"] = ("red1", "bptt_grid")[d["dwh"]]
@@ -407,7 +412,9 @@ class QLearner:
         3: online relu(fc1(inputs)) as (B, T+1, n, 64). After a TD(lambda) step (last_plan()["td_lambda"] == 1):
         4: y', the target network's mixed value at step t + 1, as (B, T, 1), or (B, T, n) without a mixer;
         5: the lambda targets in the same shape. After a prioritized-replay step (last_plan()["per"] == 1): 6: the
-        unweighted |td * mask| the priority write-back summed, as (B, T, 1) (no mixer: summed over the agents)."""
+        unweighted |td * mask| the priority write-back summed, as (B, T, 1) (no mixer: summed over the agents).
+        After a step of the two-layer hypernet (last_plan()["hyper_layers"] == 2): 7: the online net's layer-1
+        pre-activations [hyper_w_1.0 | hyper_w_final.0] as (B, T, 2 * hypernet_embed)."""
         B, Tp = self._last_batch
         n, A = self.args.n_agents, self.args.n_actions
         cnt = ctypes.c_int64()
@@ -419,7 +426,7 @@ class QLearner:
             return out.view(Tp, B, n, A).permute(1, 0, 2, 3)
         if which == 3:
             return out.view(Tp, B, n, -1).permute(1, 0, 2, 3)
-        if which in (4, 5, 6):
+        if which in (4, 5, 6, 7):
             return out.view(Tp - 1, B, -1).permute(1, 0, 2)
         return out.view(Tp - 1, B, n).permute(1, 0, 2)
 
