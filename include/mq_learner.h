@@ -12,6 +12,8 @@
  *   mq_train_step        QLearner.train(batch, t_env, episode_num)      src/learners/q_learner.py:37-116
  *   mq_forward_backward  q_learner.py:39-101 (loss + backward, before clip/step)
  *   mq_apply             q_learner.py:102-103 (clip_grad_norm_ + RMSprop.step) and the stats of :109-116
+ *   mq_set_adam          (opt-in, not in the reference) torch.optim.Adam in RMSprop's place at q_learner.py:30,103;
+ *                        mq_adam_update is the same step on caller-owned buffers, mq_opt_step its step count
  *   mq_update_targets    QLearner._update_targets                       src/learners/q_learner.py:118-122
  *   mq_mac_forward       BasicMAC.forward(ep_batch, t)                   src/controllers/basic_controller.py:40-75
  *   mq_agent_forward     RNNAgent.forward(inputs, hidden_state)          src/modules/agents/rnn_agent.py:27-36
@@ -126,7 +128,8 @@ int mq_bind(mq_handle* h, float* online, float* target, float* grad, float* sq_a
 /* Loss + backward of QLearner.train on `batch`: writes UNNORMALISED gradients d(sum (td*m)^2)/dtheta and the
  * MQ_NSUMS partial sums into grad. Data-parallel callers all-reduce grad (whole buffer) between the two calls. */
 int mq_forward_backward(mq_handle* h, const mq_replay* batch, void* stream);
-/* Normalise by sum(m), clip_grad_norm_(grad_norm_clip), RMSprop(lr, alpha, eps) step, write stats. */
+/* Normalise by sum(m), clip_grad_norm_(grad_norm_clip), RMSprop(lr, alpha, eps) step (Adam's after mq_set_adam),
+ * write stats. */
 int mq_apply(mq_handle* h, void* stream);
 /* mq_forward_backward + mq_apply in one call (with a communicator attached, the all-reduce between them too). */
 int mq_train_step(mq_handle* h, const mq_replay* batch, void* stream);
@@ -153,6 +156,35 @@ int mq_comm_use(mq_handle* h, void* nccl_comm);
 int mq_comm_create(const uint8_t* id, int32_t rank, int32_t world, void** nccl_comm);
 int mq_comm_free(void* nccl_comm);
 int mq_update_targets(mq_handle* h, void* stream);
+
+/* Adam, an opt-in (the reference's learner has RMSprop only; pymarl2 / epymarl configs say optimizer: adam).
+ * mq_set_adam makes mq_apply (and so mq_train_step) take torch.optim.Adam's step instead of RMSprop's, until
+ * mq_set_adam(h, NULL) goes back (sticky). Everything in front of the apply is untouched, and so are the
+ * normalisation by sum(m), clip_grad_norm_ and the stats; per element, in fp32 and torch's operand order
+ * (non-amsgrad, non-maximize):
+ *   gi = (g / sum(m)) * coef;  g = gi             (the clipped gradient, WITHOUT the decay term)
+ *   gd = weight_decay != 0 ? gi + weight_decay * p : gi          (L2 decay: after the clip, not in grad_norm)
+ *   m += (1 - beta1) * (gd - m);  v = v * beta2 + (1 - beta2) * gd * gd
+ *   p += -(lr / (1 - beta1^t)) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps))
+ * with t = step + 1 the 1-based number of this step; lr / (1 - beta1^t), sqrt(1 - beta2^t), 1 - beta1 and 1 - beta2
+ * are formed in double on the host and cast to float once; lr and the betas enter that arithmetic as the shortest
+ * decimal that rounds to the given float (0.999f stands for 0.999, the Python float torch would be given: 1 - beta2
+ * from the widened float would be off by 1.3e-5 of itself). exp_avg (m): [P] device floats, borrowed like mq_bind's
+ * pointers; mq_bind's sq_avg serves as exp_avg_sq (v). step: the steps already applied (0: a fresh optimiser);
+ * every mq_apply uses step + 1 and then increments the count, which mq_opt_step reports (-1: NULL handle; 0 while
+ * RMSprop is selected). mq_config.optim_alpha / optim_eps are ignored while Adam is set. Data parallelism
+ * (mq_set_data_parallel, an attached communicator), PER, TD(lambda), Huber and both hypernet depths work as before:
+ * none of them touches the apply. MQ_ERR_ARG: exp_avg NULL, a beta outside [0, 1) or NaN, eps <= 0 or NaN,
+ * weight_decay < 0 or NaN, step < 0. */
+typedef struct mq_adam { float* exp_avg; float beta1, beta2, eps, weight_decay; int64_t step; } mq_adam;
+int mq_set_adam(mq_handle* h, const mq_adam* a);
+int64_t mq_opt_step(const mq_handle* h);
+/* One Adam step (the arithmetic above with gi = g: no normalisation, no clip, no stats) on caller-owned device
+ * buffers of n floats each, one launch on `stream`; step: the 1-based number of this step. The buffers need no
+ * alignment beyond a float's. MQ_ERR_ARG: step < 1, a NULL pointer, n < 0, lr < 0 or NaN, and mq_set_adam's range
+ * checks. */
+int mq_adam_update(float* p, float* g, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, int64_t step, void* stream);
 
 /* Prioritized episode replay (PER), an opt-in the reference lacks. Priorities live on the device and never reach the
  * host: mq_per_sample draws, the next train step weights its loss and writes the new priorities back.

@@ -18,7 +18,8 @@
 //   dwh      gemm  [dW_hyper | db_hyper] = dHYP^T state                   split-K (QMIX only)
 //   reduce   deterministic two-pass slab sums -> flat gradient buffer (+ loss sums), per-block sums of squares
 //   --- (data-parallel all-reduce of the gradient buffer happens here, in the caller)
-//   apply    / sum(mask), clip_grad_norm_, RMSprop
+//   apply    / sum(mask), clip_grad_norm_, RMSprop (mq_set_adam: Adam, apply_adam_kernel)
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -155,6 +156,10 @@ struct mq_handle {
   float *A1 = nullptr, *dA1 = nullptr;
   bool have_h2 = false;   // the last step ran it (mq_copy_intermediate 7)
   int hyper_layers = 0;   // of the last step (mq_last_hyper_layers)
+  // Adam (mq_set_adam): mq_apply launches apply_adam_kernel with ad.exp_avg beside sq; adam_step counts the steps applied
+  bool adam = false;
+  mq_adam ad{};
+  int64_t adam_step = 0;
   int num_cu = 0;
   // timing: a ring of `slots` steps x PH_N (start, stop) event pairs; phases outside `mask` are not recorded
   int slots = 0;
@@ -216,6 +221,53 @@ void compute_layout(mq_handle* h) {
 }
 
 int64_t align_up(int64_t x) { return (x + 63) & ~int64_t(63); }
+
+int check_adam(const char* who, float beta1, float beta2, float eps, float wd) {
+  if (!(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f))
+    return set_err(MQ_ERR_ARG, std::string(who) + ": adam betas must be in [0, 1)");
+  if (!(eps > 0.0f)) return set_err(MQ_ERR_ARG, std::string(who) + ": adam eps must be > 0");
+  if (!(wd >= 0.0f)) return set_err(MQ_ERR_ARG, std::string(who) + ": weight_decay must be >= 0");
+  return MQ_OK;
+}
+
+// The kernel's scalars for step t (1-based): the bias corrections in double, as torch forms them in Python floats,
+// each cast to float once.
+// The double a float hyper-parameter stands for: the shortest decimal that rounds to it (0.999f is 0.999, as numpy
+// prints a float32), which is the Python float the host's config held. The plain widening of 0.999f is off by 1.3e-8,
+// and that is 1.3e-5 of 1 - beta2: more than the whole error budget of exp_avg_sq.
+double decimal_of(float x) {
+  char buf[40];
+  for (int prec = 1; prec <= 9; ++prec) {
+    std::snprintf(buf, sizeof(buf), "%.*g", prec, (double)x);
+    if (std::strtof(buf, nullptr) == x) return std::strtod(buf, nullptr);
+  }
+  return (double)x;
+}
+
+AdamHP make_adam_hp(float lr, float beta1, float beta2, float eps, float wd, int64_t t, float clip, int n_agents) {
+  const double b1 = decimal_of(beta1), b2 = decimal_of(beta2);
+  const double bc1 = 1.0 - std::pow(b1, (double)t), bc2 = 1.0 - std::pow(b2, (double)t);
+  AdamHP hp;
+  hp.step_size = (float)(decimal_of(lr) / bc1);
+  hp.bc2_sqrt = (float)std::sqrt(bc2);
+  hp.beta2 = beta2;
+  hp.omb1 = (float)(1.0 - b1);
+  hp.omb2 = (float)(1.0 - b2);
+  hp.eps = eps;
+  hp.wd = wd;
+  hp.clip = clip;
+  hp.n_agents = n_agents;
+  return hp;
+}
+
+// apply_adam_kernel's grid: a thread per float4 of the body (or per scalar when the pointers disagree modulo 16 bytes),
+// at most 1024 blocks of 256
+int adam_blocks(const float* p, const float* g, const float* m, const float* v, int64_t n) {
+  const uintptr_t a = (uintptr_t)p & 15;
+  const bool same = ((uintptr_t)g & 15) == a && ((uintptr_t)m & 15) == a && ((uintptr_t)v & 15) == a;
+  const int64_t items = same ? n / 4 + 6 : n;
+  return (int)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, 1024));
+}
 
 Dims make_dims(const mq_handle* h, const mq_replay* b) {
   return mq::make_dims(h->cfg, b->batch_size, b->t_len, b->t_stride);
@@ -928,13 +980,63 @@ int mq_apply(mq_handle* h, void* stream) {
                        h->w.norm_part);
     MQ_HIP(hipGetLastError());
   }
-  OptHP hp{h->cfg.lr, h->cfg.optim_alpha, h->cfg.optim_eps, h->cfg.grad_norm_clip, h->cfg.n_agents};
-  int blocks = (int)std::min<int64_t>((h->P + 255) / 256, 1024);
-  hipLaunchKernelGGL(apply_kernel, dim3(blocks), dim3(256), 0, s, h->on, h->grad, h->sq, h->P,
-                     (const float*)h->w.norm_part, h->n_norm_part, hp, h->stats, (const int*)nullptr);
-  MQ_HIP(hipGetLastError());
+  if (h->adam) {
+    const AdamHP hp = make_adam_hp(h->cfg.lr, h->ad.beta1, h->ad.beta2, h->ad.eps, h->ad.weight_decay,
+                                   h->adam_step + 1, h->cfg.grad_norm_clip, h->cfg.n_agents);
+    hipLaunchKernelGGL(apply_adam_kernel, dim3(adam_blocks(h->on, h->grad, h->ad.exp_avg, h->sq, h->P)), dim3(256), 0,
+                       s, h->on, h->grad, h->ad.exp_avg, h->sq, h->P, (const float*)h->w.norm_part, h->n_norm_part, hp,
+                       h->stats, (const int*)nullptr);
+    MQ_HIP(hipGetLastError());
+    ++h->adam_step;
+  } else {
+    OptHP hp{h->cfg.lr, h->cfg.optim_alpha, h->cfg.optim_eps, h->cfg.grad_norm_clip, h->cfg.n_agents};
+    int blocks = (int)std::min<int64_t>((h->P + 255) / 256, 1024);
+    hipLaunchKernelGGL(apply_kernel, dim3(blocks), dim3(256), 0, s, h->on, h->grad, h->sq, h->P,
+                       (const float*)h->w.norm_part, h->n_norm_part, hp, h->stats, (const int*)nullptr);
+    MQ_HIP(hipGetLastError());
+  }
   pt.end();
   ++h->tstep;
+  return MQ_OK;
+}
+
+int mq_set_adam(mq_handle* h, const mq_adam* a) {
+  if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
+  if (!a) {   // back to RMSprop
+    h->adam = false;
+    h->ad = mq_adam{};
+    h->adam_step = 0;
+    return MQ_OK;
+  }
+  if (!a->exp_avg) return set_err(MQ_ERR_ARG, "mq_set_adam: exp_avg is NULL");
+  if ((uintptr_t)a->exp_avg & 3) return set_err(MQ_ERR_ARG, "mq_set_adam: exp_avg is not aligned to a float");
+  const int rc = check_adam("mq_set_adam", a->beta1, a->beta2, a->eps, a->weight_decay);
+  if (rc) return rc;
+  if (a->step < 0) return set_err(MQ_ERR_ARG, "mq_set_adam: step must be >= 0");
+  h->ad = *a;
+  h->adam_step = a->step;
+  h->adam = true;
+  return MQ_OK;
+}
+
+int64_t mq_opt_step(const mq_handle* h) { return h ? h->adam_step : -1; }
+
+int mq_adam_update(float* p, float* g, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+  if (!p || !g || !exp_avg || !exp_avg_sq) return set_err(MQ_ERR_ARG, "NULL pointer in mq_adam_update");
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 3)
+    return set_err(MQ_ERR_ARG, "mq_adam_update: a pointer is not aligned to a float");
+  if (n < 0) return set_err(MQ_ERR_ARG, "mq_adam_update: n must be >= 0");
+  if (step < 1) return set_err(MQ_ERR_ARG, "mq_adam_update: step is the 1-based step number (>= 1)");
+  if (!(lr >= 0.0f)) return set_err(MQ_ERR_ARG, "mq_adam_update: lr must be >= 0");
+  const int rc = check_adam("mq_adam_update", beta1, beta2, eps, weight_decay);
+  if (rc) return rc;
+  if (n == 0) return MQ_OK;
+  const AdamHP hp = make_adam_hp(lr, beta1, beta2, eps, weight_decay, step, 0.0f, 1);
+  hipLaunchKernelGGL(apply_adam_kernel, dim3(adam_blocks(p, g, exp_avg, exp_avg_sq, n)), dim3(256), 0,
+                     (hipStream_t)stream, p, g, exp_avg, exp_avg_sq, n, (const float*)nullptr, 0, hp, (float*)nullptr,
+                     (const int*)nullptr);
+  MQ_HIP(hipGetLastError());
   return MQ_OK;
 }
 

@@ -183,6 +183,99 @@ __global__ __launch_bounds__(256) void apply_kernel(float* __restrict__ p, float
   }
 }
 
+// Adam (mq_set_adam / mq_adam_update). The host forms step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t),
+// omb1 = 1 - beta1 and omb2 = 1 - beta2 in double, as torch forms them in Python floats, and casts each once.
+struct AdamHP {
+  float step_size, bc2_sqrt, beta2, omb1, omb2, eps, wd, clip;
+  int n_agents;
+};
+
+// One element of torch.optim.Adam's step (non-amsgrad, non-maximize, non-capturable), op for op in its operand order;
+// no contraction into FMAs, so every product and sum is rounded as torch's own fp32 ops round it. The weight decay is
+// L2 (added to the gradient after clipping); the gradient written back is the clipped one without it.
+MQ_DEV void adam_elem(float& p, float& g, float& m, float& v, float inv, float coef, const AdamHP& hp) {
+#pragma clang fp contract(off)
+  const float gi = (g * inv) * coef;
+  const float gd = hp.wd != 0.0f ? gi + hp.wd * p : gi;
+  const float m1 = m + hp.omb1 * (gd - m);
+  const float v1 = v * hp.beta2 + hp.omb2 * (gd * gd);
+  const float den = sqrtf(v1) / hp.bc2_sqrt + hp.eps;
+  p = p + (-hp.step_size) * (m1 / den);
+  g = gi;
+  m = m1;
+  v = v1;
+}
+
+// apply_kernel's prologue (halt word, norm re-derived by every block from the same partials in the same order, clip
+// coefficient, block 0's eight stats) with Adam as the per-element update: four streams in, four out. The elements
+// between the first 16-byte boundary and the last go as float4 (when the four pointers agree modulo 16 bytes; else
+// everything is scalar), the head and tail as scalars; a thread's first float4 loads are issued before the norm is
+// known. part == NULL: the standalone step (mq_adam_update): no prologue, no stats, no sums tail behind g,
+// inv = coef = 1. The update is elementwise, so the result does not depend on the vector width or the grid.
+__global__ __launch_bounds__(256) void apply_adam_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                         const float* __restrict__ part, int npart, AdamHP hp,
+                                                         float* __restrict__ stats, const int* __restrict__ halt) {
+  if (halt && *halt != 0) return;
+  __shared__ float sh[2];
+  const uintptr_t ap = (uintptr_t)p & 15;
+  const bool same = ((uintptr_t)g & 15) == ap && ((uintptr_t)m & 15) == ap && ((uintptr_t)v & 15) == ap;
+  const int64_t lead = (int64_t)(((16 - ap) >> 2) & 3);
+  const int64_t head = same && lead < n ? lead : n;                         // scalars before the float4 body
+  const int64_t nv = (n - head) >> 2;                                       // float4 items of the body
+  const int64_t tail0 = head + 4 * nv, ns = head + (n - tail0);             // scalar items: head, then tail
+  const int64_t q0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  const bool have0 = q0 < nv;
+  const f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  auto ld4 = [&](const float* b, int64_t q) { return *(const f32x4*)(b + head + 4 * q); };
+  const f32x4 g0 = have0 ? ld4(g, q0) : z4, m0 = have0 ? ld4(m, q0) : z4, v0 = have0 ? ld4(v, q0) : z4,
+              p0 = have0 ? ld4(p, q0) : z4;
+  float inv = 1.0f, coef = 1.0f, norm = 0.0f, msum = 1.0f;
+  const float* sums = g + n;   // MQ_NSUMS tail (read with part only)
+  if (part) {
+    msum = sums[1];
+    if (threadIdx.x < 64) {
+      float s = 0.0f;
+      for (int i = threadIdx.x; i < npart; i += 64) s += part[i];
+      s = wave_sum(s);
+      if (threadIdx.x == 0) sh[0] = s;
+    }
+    __syncthreads();
+    inv = 1.0f / msum;
+    norm = sqrtf(sh[0]) * inv;
+    coef = fminf(hp.clip / (norm + 1e-6f), 1.0f);
+  }
+  auto upd4 = [&](int64_t q, f32x4 gv, f32x4 mv, f32x4 vv, f32x4 pv) {
+    float ge[4] = {gv.x, gv.y, gv.z, gv.w}, me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w},
+          pe[4] = {pv.x, pv.y, pv.z, pv.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) adam_elem(pe[e], ge[e], me[e], ve[e], inv, coef, hp);
+    const int64_t i = head + 4 * q;
+    *(f32x4*)(g + i) = f32x4{ge[0], ge[1], ge[2], ge[3]};
+    *(f32x4*)(m + i) = f32x4{me[0], me[1], me[2], me[3]};
+    *(f32x4*)(v + i) = f32x4{ve[0], ve[1], ve[2], ve[3]};
+    *(f32x4*)(p + i) = f32x4{pe[0], pe[1], pe[2], pe[3]};
+  };
+  if (have0) upd4(q0, g0, m0, v0, p0);
+  for (int64_t q = q0 + stride; q < nv; q += stride) upd4(q, ld4(g, q), ld4(m, q), ld4(v, q), ld4(p, q));
+  for (int64_t j = q0; j < ns; j += stride) {
+    const int64_t i = j < head ? j : tail0 + (j - head);
+    float ge = g[i], me = m[i], ve = v[i], pe = p[i];
+    adam_elem(pe, ge, me, ve, inv, coef, hp);
+    g[i] = ge; m[i] = me; v[i] = ve; p[i] = pe;
+  }
+  if (part && blockIdx.x == 0 && threadIdx.x == 0) {
+    stats[0] = sums[0] / msum;                         // loss
+    stats[1] = norm;                                   // grad_norm
+    stats[2] = sums[2] / msum;                         // td_error_abs
+    stats[3] = sums[3] / (msum * (float)hp.n_agents);  // q_taken_mean
+    stats[4] = sums[4] / (msum * (float)hp.n_agents);  // target_mean
+    stats[5] = msum;
+    stats[6] = coef;
+    stats[7] = 0.0f;
+  }
+}
+
 // One BasicMAC.forward step for every (episode, agent) row: inputs [obs_t | onehot(a_{t-1}) | onehot(agent)],
 // fc1 -> relu -> GRUCell -> fc2. One 256-thread workgroup per row (rollout batches are small).
 // xin_dense != NULL: the inputs are given ([rows][I], RNNAgent.forward); otherwise they are built from the replay.

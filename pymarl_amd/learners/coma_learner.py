@@ -73,6 +73,9 @@ def make_coma_config(args, input_dim, max_batch, max_seq):
 class COMALearner:
     def __init__(self, mac, scheme, logger, args):
         self.args = args
+        if getattr(args, "optimizer", None) not in (None, "rmsprop"):
+            # the critic chain steps RMSprop in registers (include/mc_coma.h): never train on silently with another
+            raise ValueError("COMALearner supports optimizer: rmsprop only (got {}).".format(args.optimizer))
         self.n_agents = args.n_agents
         self.n_actions = args.n_actions
         self.mac = mac

@@ -6,6 +6,10 @@ both GRU unrolls, double-Q selection, mixer, masked L2 TD loss, BPTT, clip_grad_
 launch sequence of hand-written HIP kernels in libmq_learner.so (include/mq_learner.h); torch only owns the
 device buffers. There is no CPU path: a learner that is not on a HIP device raises.
 
+Opt-in `optimizer: adam` (pymarl2's key; `weight_decay`, `adam_betas`, `adam_eps`): the step's last launch is then
+torch.optim.Adam's update (apply_adam_kernel, mq_set_adam) and `self.optimiser` a real torch.optim.Adam whose exp_avg /
+exp_avg_sq are views into two flat buffers, so opt.th has torch's format both ways. Without the key nothing changes.
+
 Data parallel: with `args.learner_dp = True` and torch.distributed initialised (RCCL, one process
 per GPU), every rank calls train() with the SAME GLOBAL sample, as run.py:207-219 does unchanged (ranks share the
 seed, so the sampled ids agree; ids and contents checked on a call-count schedule, `args.learner_dp_check`); the
@@ -24,7 +28,7 @@ import ctypes
 import numpy as np
 
 import torch as th
-from torch.optim import RMSprop
+from torch.optim import Adam, RMSprop
 
 from .. import _lib
 from ..components.episode_buffer import PrioritizedBatch, is_replay_view
@@ -35,6 +39,7 @@ from ..modules.mixers.vdn import VDNMixer
 
 MIXER_IDS = {None: _lib.MIXER_NONE, "vdn": _lib.MIXER_VDN, "qmix": _lib.MIXER_QMIX}
 Q_TARGETS = ("one_step", "td_lambda")
+OPTIMIZERS = ("rmsprop", "adam")
 _FIELDS = [("obs", th.float32), ("state", th.float32), ("actions", th.int64), ("avail_actions", th.int32),
            ("reward", th.float32), ("terminated", th.uint8), ("filled", th.int64)]
 
@@ -76,6 +81,30 @@ def make_config(args, mixer, input_dim=None, max_batch=1, max_seq=2):
     if mixer == _lib.MIXER_QMIX:
         cfg.hypernet_layers, cfg.hypernet_embed = hypernet_config(args)
     return cfg
+
+
+def optimizer_config(args):
+    """The optimiser keys, named as pymarl2 names them: (name, kwargs). optimizer absent or "rmsprop": ("rmsprop",
+    None), the reference's RMSprop(lr, optim_alpha, optim_eps). "adam": torch.optim.Adam's lr, betas (adam_betas,
+    default (0.9, 0.999)), eps (adam_eps, default 1e-8: torch's, pymarl2 does not pass optim_eps to Adam) and
+    weight_decay (default 0, L2). Anything else, or adam_amsgrad: True, raises ValueError."""
+    name = getattr(args, "optimizer", None)
+    name = "rmsprop" if name is None else name
+    if name not in OPTIMIZERS:
+        raise ValueError("optimizer {} not recognised (one of {}).".format(name, ", ".join(OPTIMIZERS)))
+    if name == "rmsprop":
+        return name, None
+    if getattr(args, "adam_amsgrad", False):
+        raise ValueError("adam_amsgrad is not supported (optimizer: adam runs torch.optim.Adam's non-amsgrad step).")
+    betas = tuple(float(b) for b in getattr(args, "adam_betas", (0.9, 0.999)))
+    eps, wd = float(getattr(args, "adam_eps", 1e-8)), float(getattr(args, "weight_decay", 0.0))
+    if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+        raise ValueError("adam_betas must be two values in [0, 1), got {}.".format(betas))
+    if not eps > 0.0:
+        raise ValueError("adam_eps must be > 0, got {}.".format(eps))
+    if not wd >= 0.0:
+        raise ValueError("weight_decay must be >= 0, got {}.".format(wd))
+    return name, dict(lr=args.lr, betas=betas, eps=eps, weight_decay=wd)
 
 
 def is_per_batch(batch):
@@ -179,7 +208,12 @@ class QLearner:
                 raise ValueError("Mixer {} not recognised.".format(args.mixer))
             self.params += list(self.mixer.parameters())
             self.target_mixer = copy.deepcopy(self.mixer)
-        self.optimiser = RMSprop(params=self.params, lr=args.lr, alpha=args.optim_alpha, eps=args.optim_eps)
+        # optimizer: adam is an opt-in (optimizer_config); without the key this is the reference's line
+        self.optim_name, adam_kw = optimizer_config(args)
+        if adam_kw is None:
+            self.optimiser = RMSprop(params=self.params, lr=args.lr, alpha=args.optim_alpha, eps=args.optim_eps)
+        else:
+            self.optimiser = Adam(params=self.params, **adam_kw)
         self.target_mac = copy.deepcopy(mac)
         self.log_stats_t = -self.args.learner_log_interval - 1
         self.dp = bool(getattr(args, "learner_dp", False))
@@ -207,12 +241,14 @@ class QLearner:
         P = self.n_params
         self._grad = th.zeros(P + _lib.NSUMS, dtype=th.float32, device=dev)
         self._sq = th.zeros(P, dtype=th.float32, device=dev)
+        # Adam's first moment (exp_avg); its second (exp_avg_sq) lives in _sq, where RMSprop's square_avg does
+        self._m = th.zeros(P, dtype=th.float32, device=dev) if self.optim_name == "adam" else None
         self._stats = th.zeros(_lib.NSTATS, dtype=th.float32, device=dev)
         self._curmax = None
         self._relink()
 
     def _relink(self):
-        """Point module params, .grad and the optimiser's square_avg at the flat buffers."""
+        """Point module params, .grad and the optimiser's square_avg (Adam: exp_avg, exp_avg_sq) at the flat buffers."""
         Pa = sum(p.numel() for p in self.mac.agent.parameters())
         rebind(self._mods, self._online)
         rebind(self._tmods, self._target)
@@ -227,8 +263,13 @@ class QLearner:
             n = p.numel()
             p.grad = self._grad[o:o + n].view_as(p)
             st = self.optimiser.state[p]
-            st["square_avg"] = self._sq[o:o + n].view_as(p)
-            st["step"] = self._step_t   # one shared counter: train() increments it once, not once per parameter
+            if self.optim_name == "adam":   # torch.optim.Adam's state keys, in its order
+                st["step"] = self._step_t
+                st["exp_avg"] = self._m[o:o + n].view_as(p)
+                st["exp_avg_sq"] = self._sq[o:o + n].view_as(p)
+            else:
+                st["square_avg"] = self._sq[o:o + n].view_as(p)
+                st["step"] = self._step_t   # one shared counter: train() increments it once, not once per parameter
             o += n
         self._handle = None
 
@@ -262,6 +303,12 @@ class QLearner:
             self._curmax = th.zeros(Tmax * need_b * self.args.n_agents, dtype=th.int32, device=self._online.device)
             _lib.check(h.lib.mq_bind(h.h, _lib.ptr(self._online), _lib.ptr(self._target), _lib.ptr(self._grad),
                                      _lib.ptr(self._sq), _lib.ptr(self._stats), _lib.ptr(self._curmax)))
+            if getattr(self, "optim_name", "rmsprop") == "adam":
+                # with the CURRENT step count: a handle rebuilt for a larger batch must not restart the bias correction
+                g = self.optimiser.param_groups[0]
+                ad = _lib.MQAdam(exp_avg=self._m.data_ptr(), beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"],
+                                 weight_decay=g["weight_decay"], step=self._opt_steps)
+                _lib.check(h.lib.mq_set_adam(h.h, ctypes.byref(ad)))
             h.dp_on = False
             h.native = False
             if self._dp_active() and native_comm_wanted(self._online.device):
@@ -338,6 +385,8 @@ class QLearner:
         self._target = self._target.to(dev)
         self._grad = self._grad.to(dev)
         self._sq = self._sq.to(dev)
+        if self._m is not None:
+            self._m = self._m.to(dev)
         self._stats = self._stats.to(dev)
         self._relink()
 
@@ -359,13 +408,23 @@ class QLearner:
         if self.mixer is not None:
             self.mixer.load_state_dict(th.load("{}/mixer.th".format(path), map_location=ml, weights_only=True))
         sd = th.load("{}/opt.th".format(path), map_location=ml, weights_only=True)
+        # an opt.th of the other optimiser would load without complaint (torch checks only the group sizes) and
+        # leave the moments this learner steps with at zero
+        groups = sd.get("param_groups") or [{}]
+        wrote = "adam" if "betas" in groups[0] else "rmsprop" if "alpha" in groups[0] else None
+        if wrote is not None and wrote != self.optim_name:
+            raise ValueError("{}/opt.th was written by {}, but this learner runs optimizer: {}.".format(
+                path, {"adam": "Adam", "rmsprop": "RMSprop"}[wrote], self.optim_name))
         self.optimiser.load_state_dict(sd)
+        # load_state_dict replaced the state tensors: copy back into the flat buffers
+        flat = {"exp_avg": self._m, "exp_avg_sq": self._sq} if self.optim_name == "adam" else {"square_avg": self._sq}
         o = 0
-        for p in self.params:   # load_state_dict replaced the state tensors: copy back into the flat buffer
+        for p in self.params:
             n = p.numel()
             st = self.optimiser.state.get(p, {})
-            if "square_avg" in st:
-                self._sq[o:o + n].copy_(st["square_avg"].reshape(-1))
+            for key, buf in flat.items():
+                if key in st:
+                    buf[o:o + n].copy_(st[key].reshape(-1))
             o += n
         steps = [float(self.optimiser.state[p]["step"]) for p in self.params if "step" in self.optimiser.state[p]]
         self._opt_steps = int(steps[0]) if steps else 0
