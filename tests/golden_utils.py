@@ -135,3 +135,28 @@ class ComaCase:
         b = OrderedDict((k, v[ids]) for k, v in self.data.items())
         max_t = int(b["filled"].sum(1).max())
         return OrderedDict((k, v[:, :max_t]) for k, v in b.items()), ids
+
+
+class SynthComaCase(ComaCase):
+    """A ComaCase without a reference fixture, as SynthCase is to Case: replay (ragged, episodes from one step on),
+    weights and epsilon from `seed`, n_episodes = B so that every step trains on episodes 0..B-1. For the edge shapes
+    of tests/coma_ref64.py, checked against the float64 reference and the oracle only."""
+
+    def __init__(self, name, n, A, O, S, T, B, seed, mask_before_softmax, epsilon=(0.5, 0.3),
+                 target_update_interval=200):
+        from oracle.coma_np import critic_input_dim, critic_param_shapes
+        self.name = name
+        self.n, self.A, self.O, self.S, self.T, self.B = n, A, O, S, T, B
+        self.n_episodes, self.steps, self.ragged = B, len(epsilon), True
+        self.mask_before_softmax = bool(mask_before_softmax)
+        self.target_update_interval = target_update_interval
+        self.data = make_replay(B, T, n, A, O, S, seed=seed, ragged=True, min_len=1)
+        self.I = O + A + n
+        self.K = critic_input_dim(n, A, O, S)
+        self.agent_shapes = agent_param_shapes(self.I, 64, A)
+        self.critic_shapes = critic_param_shapes(self.K, A)
+        self.agent_params = init_params(self.agent_shapes, seed=seed + 1)
+        self.critic_params = init_params(self.critic_shapes, seed=seed + 201)
+        self.sampler_seed = seed + 2
+        self.epsilon = [float(e) for e in epsilon]
+        self.z = {"ids": np.stack([np.arange(B)] * self.steps)}

@@ -3,8 +3,8 @@
 `ref64_step` restates the step's loss in torch float64 on the CPU and lets autograd differentiate it: agent unroll
 over `[obs | last-action one-hot | agent id]`, fc1 -> relu -> GRU cell -> fc2, double-Q or max target, QMixer / sum /
 none, the -9999999 masks and the masked L2 loss. It shares no hand-derived backward with the numpy oracle
-(oracle/qlearner_np.py) or with the kernels; only constants are taken from the oracle. Huber, TD(lambda) and COMA are
-out of scope.
+(oracle/qlearner_np.py) or with the kernels; only constants are taken from the oracle. Huber and TD(lambda) are out
+of scope; COMA's train() has its own reference on the same gate in tests/coma_ref64.py.
 
 The gate (DESIGN.md "Parity"): every block named by `grad_blocks` is judged on its own max,
 `block_errors` = max|got - ref| / max|ref| per block, against `tolerances(e32)` where e32 is the fp32 numpy
@@ -210,12 +210,13 @@ def grad_blocks(case):
     return blocks
 
 
-def block_errors(got_flat, ref_named, case):
+def block_errors(got_flat, ref_named, case, blocks=None):
     """{block: max|got - ref| / max|ref|} of a flat gradient against a named float64 one. A block whose reference max
-    is exactly 0 (a last-action column block of actions never taken) is measured on its parent tensor's max."""
+    is exactly 0 (a last-action column block of actions never taken) is measured on its parent tensor's max.
+    blocks: another table over case.unflatten's tensors than grad_blocks(case) (tests/coma_ref64.py: the critic's)."""
     got = case.unflatten(np.asarray(got_flat, np.float64))
     out = OrderedDict()
-    for name, (k, idx) in grad_blocks(case).items():
+    for name, (k, idx) in (grad_blocks(case) if blocks is None else blocks).items():
         ref = np.asarray(ref_named[k], np.float64)
         scale = float(np.abs(ref[idx]).max())
         if scale == 0.0:

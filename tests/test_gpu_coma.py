@@ -5,7 +5,8 @@ Runs through the product path: COMALearner.train -> libmq_learner.so (mc_train_s
 * teacher-forced steps: before every train() the GPU learner is loaded with the oracle's agent / critic /
   target-critic parameters and both RMSprop states, so each step starts from the same state. Checked per step: the
   critic's Q values the actor used and the TD(lambda) targets, the policy, the nine stats, the agent's clipped
-  gradient, and the agent update as RMSprop of the GPU's own gradient (exact up to rounding, as in the QMIX test).
+  gradient, and the agent update as RMSprop of the GPU's own gradient (exact up to rounding, as in the QMIX test);
+  on the tiny cases the critic's square_avg per block against the float64 reference (tests/coma_ref64.py).
   One train() is T dependent critic optimiser steps: fp32 summation-order noise grows along that chain as it does
   between the oracle and the reference (tests/test_coma_oracle.py), so the critic-side tolerances scale with T.
 * free-running step 0 vs the reference golden run, at the oracle test's tolerances.
@@ -14,6 +15,7 @@ import numpy as np
 import pytest
 import torch as th
 
+from tests import coma_ref64, ref64
 from tests.golden_utils import COMA_STATS, ComaCase
 from tests.gpu_helpers import set_switch
 
@@ -64,6 +66,7 @@ def test_coma_teacher_forced(coma_cases, name, steps):
         nb, _ = c.batch(k)
         load_state(learner, o)
         pa, asq = o.flat("agent").astype(np.float64), o.flat("sq").astype(np.float64)
+        start = tuple(o.flat(w) for w in ("agent", "critic", "target_critic", "sq", "critic_sq"))
         mac.action_selector.epsilon = c.epsilon[k]
         learner.train(batch, 1000 * (k + 1), 8 * k)
         st = learner.last_stats()
@@ -94,6 +97,18 @@ def test_coma_teacher_forced(coma_cases, name, steps):
         dc = np.abs(learner._critic.cpu().numpy() - o.flat("critic")).max()
         assert dc <= (5e-4 * 20 if not long_chain else 5e-4 * c.T), (name, k, dc)
         assert rel(learner._tcritic.cpu().numpy(), o.flat("target_critic")) < (1e-4 if not long_chain else 1e-1)
+        if not long_chain:
+            # the critic's square_avg (every step's g^2) per critic block, judged as tests/test_gpu_coma_blocks.py
+            # judges it: against the float64 reference from the same state, within min(1e-5, 16 max(e32, 2e-7)) of
+            # the block's max, e32 the error of the oracle's own o.flat("critic_sq") on that block
+            r = coma_ref64.coma_ref64_step(c, *start, nb, c.epsilon[k])
+            view, blocks = coma_ref64.critic_view(c), coma_ref64.coma_blocks(c)["critic"]
+            e32 = ref64.block_errors(o.flat("critic_sq"), r.critic_sq, view, blocks)
+            errs = ref64.block_errors(learner._csq.cpu().numpy(), r.critic_sq, view, blocks)
+            print(name, k, "critic square_avg: worst err / e32",
+                  max((errs[b] / max(e32[b], ref64.E32_FLOOR), b) for b in errs))
+            over = ref64.failures(errs, ref64.tolerances(e32))
+            assert not over, (name, k, over)
 
 
 @pytest.mark.parametrize("name", ["coma_tiny", "coma_cfg5"])
