@@ -225,19 +225,24 @@ int mq_set_per(mq_handle* h, const mq_per* per);
 int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, void* stream);
 
 /* BasicMAC.forward(ep_batch, t) for every episode of `batch`: h_in/h_out [batch*n][64] (h_in may equal
- * h_out), q_out [batch*n][n_actions]; which = 0 online params, 1 target params. */
+ * h_out), q_out [batch*n][n_actions]; which = 0 online params, 1 target params (MQ_ERR_STATE when none are bound).
+ * MQ_ERR_ARG as mq_train_step gives it: a host id (ep_ids_host) outside [0, n_episodes), or a batch without ids
+ * whose batch_size exceeds n_episodes. */
 int mq_mac_forward(mq_handle* h, const mq_replay* batch, int32_t t, const float* h_in, float* h_out,
                    float* q_out, int32_t which, void* stream);
 /* RNNAgent.forward(inputs, hidden) (rnn_agent.py:27-36) on given inputs [rows][input_dim]. */
 int mq_agent_forward(mq_handle* h, const float* inputs, int32_t rows, const float* h_in, float* h_out,
                      float* q_out, int32_t which, void* stream);
-/* argmax over available actions (unavailable = -inf, first index on ties) of q [rows][n_actions]. */
+/* argmax over available actions (avail != 0; unavailable = -inf, first index on ties) of q [rows][n_actions], as
+ * torch's max(dim) takes it: a NaN at an available action is the maximum (the first such index); a NaN at an
+ * unavailable action is masked; a row with no available action gives 0. */
 int mq_greedy_actions(const float* q, const int32_t* avail, int64_t* out, int32_t rows, int32_t n_actions,
                       void* stream);
 
 /* QMixer.forward(agent_qs, states) outside train(): mixer = the mixer's parameters in QMixer.parameters() order
  * (hyper_w_1.weight .. V.2.bias, the MQ_P_HW1_W .. MQ_P_V2_B block), agent_qs [rows][n_agents], states
- * [rows][state_dim], q_tot [rows]. */
+ * [rows][state_dim], q_tot [rows]. n_agents and embed_dim in [1, 64]; MQ_ERR_ARG when the LDS staging of four rows,
+ * 16 (state_dim + embed_dim (n_agents + 3)) bytes, passes the 160 KB of a CU. */
 int mq_qmix_forward(const float* mixer, int32_t n_agents, int32_t state_dim, int32_t embed_dim,
                     const float* agent_qs, const float* states, float* q_tot, int32_t rows, void* stream);
 /* The same for a two-layer QMixer (hypernet_layers = 2): mixer = its parameters in parameters() order

@@ -278,7 +278,7 @@ Rep make_rep(const mq_replay* b) {
   r.obs = b->obs; r.state = b->state; r.actions = b->actions; r.avail = b->avail_actions; r.reward = b->reward;
   r.term = b->terminated; r.filled = b->filled; r.ep_ids = b->ep_ids; r.avail_bits = b->avail_bits;
   r.nids = 0;
-  if (b->ep_ids_host && b->batch_size <= MQ_INLINE_IDS) {   // ids in the kernel arguments (check_batch validated)
+  if (b->ep_ids_host && b->batch_size <= MQ_INLINE_IDS) {   // ids in the kernel arguments (check_ids validated)
     r.nids = b->batch_size;
     for (int i = 0; i < b->batch_size; ++i) r.ids[i] = (int32_t)b->ep_ids_host[i];
   }
@@ -290,6 +290,20 @@ Lay make_lay(const mq_handle* h) {
   for (int i = 0; i < LAY_N; ++i) L.o[i] = h->off[i];
   L.o[LAY_N] = h->P;
   return L;
+}
+
+// The episodes a batch names lie inside its storage: host ids (the ones make_rep copies into the kernel arguments) in
+// [0, n_episodes); a dense batch no longer than the storage. Device ids are not read on the host. Every entry point
+// that hands a batch to make_rep calls this first (check_batch for the train steps, mq_mac_forward on its own).
+int check_ids(const mq_replay* b) {
+  if (b->ep_ids_host && b->batch_size <= MQ_INLINE_IDS) {
+    for (int i = 0; i < b->batch_size; ++i)
+      if (b->ep_ids_host[i] < 0 || b->ep_ids_host[i] >= b->n_episodes)
+        return set_err(MQ_ERR_ARG, "episode id " + std::to_string(b->ep_ids_host[i]) + " outside [0, n_episodes)");
+  } else if (!b->ep_ids && b->batch_size > b->n_episodes) {
+    return set_err(MQ_ERR_ARG, "batch_size exceeds n_episodes with no episode ids");
+  }
+  return MQ_OK;
 }
 
 int check_batch(const mq_handle* h, const mq_replay* b) {
@@ -304,14 +318,7 @@ int check_batch(const mq_handle* h, const mq_replay* b) {
     return set_err(MQ_ERR_ARG, "t_len " + std::to_string(b->t_len) + " must be in [2, min(max_seq, t_stride)]");
   if ((int64_t)b->t_len * b->batch_size * h->cfg.n_agents >= (1LL << 31))
     return set_err(MQ_ERR_ARG, "batch too large for 32-bit row indices");
-  if (b->ep_ids_host && b->batch_size <= MQ_INLINE_IDS) {
-    for (int i = 0; i < b->batch_size; ++i)
-      if (b->ep_ids_host[i] < 0 || b->ep_ids_host[i] >= b->n_episodes)
-        return set_err(MQ_ERR_ARG, "episode id " + std::to_string(b->ep_ids_host[i]) + " outside [0, n_episodes)");
-  } else if (!b->ep_ids && b->batch_size > b->n_episodes) {
-    return set_err(MQ_ERR_ARG, "batch_size exceeds n_episodes with no episode ids");
-  }
-  return MQ_OK;
+  return check_ids(b);
 }
 
 struct PhaseTimer {
@@ -1210,6 +1217,7 @@ int mq_mac_forward(mq_handle* h, const mq_replay* batch, int32_t t, const float*
     return set_err(MQ_ERR_ARG, "NULL pointer in mq_mac_forward");
   if (t < 0 || t >= batch->t_stride) return set_err(MQ_ERR_ARG, "t outside the stored episode");
   if (batch->batch_size < 1) return set_err(MQ_ERR_ARG, "empty batch");
+  if (const int rc = check_ids(batch)) return rc;
   mq_replay b = *batch;
   b.t_len = std::max(2, std::min(b.t_stride, 2));
   const Dims d = make_dims(h, &b);
@@ -1260,6 +1268,10 @@ int mq_qmix_forward(const float* mixer, int32_t n_agents, int32_t state_dim, int
   if (rows == 0) return MQ_OK;
   const size_t lds = qmix_forward_lds(n_agents, state_dim, embed_dim);
   if (lds > 160 * 1024) return set_err(MQ_ERR_ARG, "mq_qmix_forward: state_dim too large for the LDS staging");
+  MQ_LDS(qmix_forward_kernel, lds);
+  if (lds > 64 * 1024)   // past the default dynamic LDS of a launch (n_agents = embed_dim = 64: 68.6 KB at least)
+    MQ_HIP(hipFuncSetAttribute((const void*)qmix_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds));
   hipLaunchKernelGGL(qmix_forward_kernel, dim3((rows + QMF_ROWS - 1) / QMF_ROWS), dim3(256), lds,
                      (hipStream_t)stream, mixer, (int)n_agents, (int)state_dim, (int)embed_dim, agent_qs, states,
                      q_tot, (int)rows);

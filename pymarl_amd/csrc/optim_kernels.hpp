@@ -348,7 +348,9 @@ __global__ __launch_bounds__(256) void mac_step_kernel(Dims d, Rep rp, const flo
   }
 }
 
-// Masked greedy argmax (unavailable = -inf, first max index), one lane per row.
+// Masked greedy argmax (unavailable = -inf, first max index), one lane per row. torch's max(dim) semantics: a NaN at
+// an available action is the maximum, and the first such index is returned (a NaN at an unavailable action is masked
+// like any other value).
 __global__ __launch_bounds__(256) void greedy_kernel(const float* __restrict__ q, const int32_t* __restrict__ avail,
                                                      int64_t* __restrict__ out, int rows, int A) {
   const int row = blockIdx.x * 256 + threadIdx.x;
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(256) void greedy_kernel(const float* __restrict__ q
   bool any = false;
   for (int a = 0; a < A; ++a) {
     const float v = avail[(int64_t)row * A + a] ? q[(int64_t)row * A + a] : -INFINITY;
-    if (!any || v > best) { best = v; arg = a; any = true; }
+    if (!any || v > best || (v != v && best == best)) { best = v; arg = a; any = true; }
   }
   out[row] = arg;
 }

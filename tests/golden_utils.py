@@ -67,14 +67,15 @@ class SynthCase(Case):
     against the reference itself; the oracle is pinned on the fixture shapes)."""
 
     def __init__(self, name, n, A, O, S, T, B, n_episodes, steps, mixer="qmix", ragged=True, min_len=1,
-                 data_seed=11, weight_seed=12, sampler_seed=13):
+                 data_seed=11, weight_seed=12, sampler_seed=13, obs_last_action=True, obs_agent_id=True):
         self.name = name
-        self.double_q = self.obs_last_action = self.obs_agent_id = True
+        self.double_q = True
+        self.obs_last_action, self.obs_agent_id = bool(obs_last_action), bool(obs_agent_id)
         self.n, self.A, self.O, self.S, self.T, self.B = n, A, O, S, T, B
         self.n_episodes, self.steps, self.mixer, self.ragged = n_episodes, steps, mixer, ragged
         self.episodes = [8 * k for k in range(steps)]
         self.data = make_replay(n_episodes, T, n, A, O, S, seed=data_seed, ragged=ragged, min_len=min_len)
-        self.I = O + A + n
+        self.I = O + (A if self.obs_last_action else 0) + (n if self.obs_agent_id else 0)
         self.agent_shapes = agent_param_shapes(self.I, 64, A)
         self.mixer_shapes = qmix_param_shapes(S, n, 32) if mixer == "qmix" else OrderedDict()
         self.agent_params = init_params(self.agent_shapes, seed=weight_seed)

@@ -86,6 +86,7 @@ def _unroll(p, obs, onehot, flags, relu_mask=None):
 def _qmix(mp, agent_qs, states, n):
     """QMixer.forward. agent_qs (B,T,n), states (B,T,S) -> y (B,T,1) and the pre-abs / pre-relu hypernet outputs."""
     B, T = agent_qs.shape[:2]
+    E = mp["hyper_w_final.weight"].shape[0]   # the module constant on every learner case; tests/act_ref64.py: 1 .. 64
     s = states.reshape(B * T, -1)
     q = agent_qs.reshape(B * T, 1, n)
     hw1 = s @ mp["hyper_w_1.weight"].T + mp["hyper_w_1.bias"]
