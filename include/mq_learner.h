@@ -15,6 +15,9 @@
  *   mq_set_adam          (opt-in, not in the reference) torch.optim.Adam in RMSprop's place at q_learner.py:30,103;
  *                        mq_adam_update is the same step on caller-owned buffers, mq_opt_step its step count
  *   mq_update_targets    QLearner._update_targets                       src/learners/q_learner.py:118-122
+ *   mq_set_soft_target   (opt-in, not in the reference) epymarl's soft target update behind every mq_apply;
+ *                        mq_soft_update is the same update on caller-owned buffers
+ *   mq_set_reward_norm   (opt-in, not in the reference) epymarl's standardise_rewards in front of q_learner.py:86
  *   mq_mac_forward       BasicMAC.forward(ep_batch, t)                   src/controllers/basic_controller.py:40-75
  *   mq_agent_forward     RNNAgent.forward(inputs, hidden_state)          src/modules/agents/rnn_agent.py:27-36
  *   mq_greedy_actions    EpsilonGreedyActionSelector greedy branch      src/components/action_selectors.py:44-62
@@ -186,6 +189,41 @@ int64_t mq_opt_step(const mq_handle* h);
 int mq_adam_update(float* p, float* g, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int64_t step, void* stream);
 
+/* Soft (Polyak) target updates, an opt-in (epymarl's target_update_interval_or_tau <= 1; the reference has the hard
+ * copy of mq_update_targets only). mq_set_soft_target(h, tau) makes every mq_apply (and so mq_train_step) end with one
+ * more launch, after the optimiser's, over the flat online / target buffers bound with mq_bind:
+ *   target = target * (1 - tau) + online * tau
+ * in fp32 with both products and the sum rounded separately (no FMA): bitwise what torch gives on the CPU for
+ * t * (1.0 - tau) + p * tau. The host forms (float)(1.0 - tau) and (float)tau, each cast once from double. Sticky
+ * until mq_set_soft_target(h, 0), which turns it off. Everything in front of it is untouched; data parallelism works
+ * unchanged (every rank holds the same parameters). MQ_ERR_ARG: NULL handle, tau outside [0, 1] or NaN.
+ * mq_last_soft_target: 1 / 0 whether the last mq_apply ran it; -1 for a NULL handle or when no step has been applied. */
+int mq_set_soft_target(mq_handle* h, double tau);
+int32_t mq_last_soft_target(const mq_handle* h);
+/* The same update on caller-owned device buffers of n floats each, one launch on `stream`; the caller passes both
+ * factors as it wants them rounded. The buffers need no alignment beyond a float's. MQ_ERR_ARG: a NULL pointer,
+ * n < 0, tau outside (0, 1] or NaN. */
+int mq_soft_update(float* target, const float* online, int64_t n, float one_minus_tau, float tau, void* stream);
+
+/* Reward standardisation with running statistics, an opt-in (epymarl's standardise_rewards). state: three device
+ * doubles [mean, var, count], initialised by the caller (epymarl: 0, 1, 1e-4), borrowed like mq_bind's pointers;
+ * sticky until mq_set_reward_norm(h, NULL) turns it off. Every mq_forward_backward / mq_train_step then begins its
+ * mixer tail with one launch of one workgroup over x = reward[:, :-1] of the batch (M = batch_size * (t_len - 1) values
+ * gathered by episode id, UNMASKED: padded steps count with the storage's zeros, duplicate ids count twice):
+ *   bm = mean(x);  bv = sum (x - bm)^2 / (M - 1)   (M = 1: 0, where torch's unbiased variance is NaN)
+ *   delta = bm - mean;  tot = count + M
+ *   mean = mean + delta * M / tot;  var = (var * count + bv * M + delta^2 * count * M / tot) / tot;  count = tot
+ * all in fp64, fixed summation order; then, with the UPDATED statistics each rounded to fp32 once,
+ *   r_std = (r - mean) / sqrtf(var)                 (fp32, no epsilon)
+ * which the step reads wherever it read the reward: the one-step target, the TD(lambda) scan, their PER and Huber
+ * forms. stats[4] (target_mean) is then on the standardised scale. Nothing is read back to the host.
+ * MQ_ERR_ARG: NULL handle, a state pointer not aligned to a double; at the step: a communicator attached or data
+ * parallelism set (each rank would standardise with its own shard's rewards).
+ * mq_last_reward_norm: 1 / 0 whether the last mq_forward_backward standardised; -1 for a NULL handle or when none
+ * has run. Like mq_last_hyper_layers these are entries of their own: mq_plan keeps its size. */
+int mq_set_reward_norm(mq_handle* h, double* state /* device, [mean, var, count] */);
+int32_t mq_last_reward_norm(const mq_handle* h);
+
 /* Prioritized episode replay (PER), an opt-in the reference lacks. Priorities live on the device and never reach the
  * host: mq_per_sample draws, the next train step weights its loss and writes the new priorities back.
  *
@@ -221,7 +259,9 @@ int mq_set_per(mq_handle* h, const mq_per* per);
  * After a prioritized-replay step (mq_plan.per = 1; MQ_ERR_STATE otherwise): 6 = |td * mask| of every transition,
  * unweighted, as [t][b] (no mixer: summed over the agents), t < t_len - 1: what the priority write-back summed.
  * After a step of the two-layer hypernet (mq_last_hyper_layers = 2; MQ_ERR_STATE otherwise): 7 = the online net's
- * first-layer pre-activations [hyper_w_1.0 | hyper_w_final.0] as [t][b][2 * hypernet_embed], t < t_len - 1. */
+ * first-layer pre-activations [hyper_w_1.0 | hyper_w_final.0] as [t][b][2 * hypernet_embed], t < t_len - 1.
+ * After a step that standardised its rewards (mq_last_reward_norm = 1; MQ_ERR_STATE otherwise): 8 = the standardised
+ * rewards the step read, as [t][b], t < t_len - 1. */
 int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, void* stream);
 
 /* BasicMAC.forward(ep_batch, t) for every episode of `batch`: h_in/h_out [batch*n][64] (h_in may equal

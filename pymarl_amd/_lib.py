@@ -29,7 +29,8 @@ EXPORTS = [
     "mq_train_step", "mq_update_targets", "mq_copy_intermediate", "mq_mac_forward", "mq_agent_forward",
     "mq_greedy_actions", "mq_set_timing", "mq_phase_times", "mq_phase_names", "mq_set_data_parallel",
     "mq_last_plan", "mq_qmix_forward", "mq_qmix_forward2", "mq_last_hyper_layers", "mq_per_sample", "mq_set_per",
-    "mq_set_adam", "mq_opt_step", "mq_adam_update",
+    "mq_set_adam", "mq_opt_step", "mq_adam_update", "mq_set_soft_target", "mq_last_soft_target", "mq_soft_update",
+    "mq_set_reward_norm", "mq_last_reward_norm",
     # include/mc_coma.h
     "mc_create", "mc_destroy", "mc_param_offsets", "mc_bind", "mc_train_step", "mc_update_targets", "mc_policy",
     "mc_copy_intermediate", "mc_set_timing", "mc_phase_times", "mc_last_critic_path", "mq_comm_unique_id", "mq_comm_attach",
@@ -159,6 +160,11 @@ def load(required=True):
         "mq_set_adam": ([vp, ctypes.POINTER(MQAdam)], ctypes.c_int),
         "mq_opt_step": ([vp], i64),
         "mq_adam_update": ([vp, vp, vp, vp, i64] + [ctypes.c_float] * 5 + [i64, vp], ctypes.c_int),
+        "mq_set_soft_target": ([vp, ctypes.c_double], ctypes.c_int),
+        "mq_last_soft_target": ([vp], i32),
+        "mq_soft_update": ([vp, vp, i64, ctypes.c_float, ctypes.c_float, vp], ctypes.c_int),
+        "mq_set_reward_norm": ([vp, vp], ctypes.c_int),
+        "mq_last_reward_norm": ([vp], i32),
         "mc_critic_forward_workspace": ([ctypes.POINTER(MCConfig), i32, i32], i64),
         "mc_critic_forward": ([vp, ctypes.POINTER(MCConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp], ctypes.c_int),
         "mq_phase_times": ([vp, ctypes.POINTER(ctypes.c_float), i32, ctypes.POINTER(i32)], ctypes.c_int),

@@ -26,6 +26,12 @@ enum { MIX_ONE_STEP = 0, MIX_LAMBDA_TARGETS = 1, MIX_LAMBDA_LOSS = 2 };
 // priority write-back. At W == 1 every value is the plain pass's, bit for bit. The plain instantiations are the
 // kernels they always were (same symbols, same argument block, same code).
 enum { MIX_PER = 4 };
+// Reward standardisation (epymarl_kernels.hpp) is one more flag, MIX_RS: the row's reward is RS[m], the standardised
+// reward reward_norm_kernel wrote, in place of rp.reward[slot]. RS is the FIRST trailing argument of such a pass,
+// ahead of (YT, G) and (W, TDA). Nothing else differs, and an instantiation without the flag is the kernel it always
+// was. Only MIX_ONE_STEP (| MIX_PER) is launched with it: under TD(lambda) the reward enters through the scan alone
+// (td_lambda_rs_kernel), and MIX_LAMBDA_LOSS takes its target from G.
+enum { MIX_RS = 8 };
 constexpr int mix_pass(int mode) { return mode & 3; }
 
 // The lambda target of row m on this lane (VDN: one per row; no mixer: one per agent lane).
@@ -55,6 +61,24 @@ MQ_DEV void tail_args(float*& YT, const float*& G, const float*& W, float*& TDA,
                       const float* wt, float* tda) {
   lambda_args(YT, G, yt, g);
   W = wt; TDA = tda;
+}
+// A MIX_RS pass: RS first, then the pass's own trailing arguments.
+template <typename... X>
+MQ_DEV void take_rs(float*& YT, const float*& G, const float*& W, float*& TDA, const float*& RS, const float* rs,
+                    X... x) {
+  RS = rs;
+  tail_args(YT, G, W, TDA, x...);
+}
+template <bool RSV, typename... X>
+MQ_DEV void tail_args_rs(float*& YT, const float*& G, const float*& W, float*& TDA, const float*& RS, X... x) {
+  if constexpr (RSV) take_rs(YT, G, W, TDA, RS, x...);
+  else tail_args(YT, G, W, TDA, x...);
+}
+// The reward of row m (storage slot `slot`) as the pass reads it.
+template <bool RSV>
+MQ_DEV float reward_of(const Rep& rp, const float* __restrict__ RS, int64_t slot, int m) {
+  if constexpr (RSV) return RS[m];
+  else return rp.reward[slot];
 }
 
 struct MixOut {
@@ -104,11 +128,13 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
                                                   LAM... lam) {
   constexpr int MODE = mix_pass(FULL);
   constexpr bool PER = (FULL & MIX_PER) != 0;
+  constexpr bool RSV = (FULL & MIX_RS) != 0;
   float* YT = nullptr;
   const float* G = nullptr;
   const float* W = nullptr;   // PER: the batch rows' importance weights [B], and |td m| out [m]
   float* TDA = nullptr;
-  tail_args(YT, G, W, TDA, lam...);
+  const float* RS = nullptr;  // MIX_RS: the standardised rewards [m]
+  tail_args_rs<RSV>(YT, G, W, TDA, RS, lam...);
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + wv;
   const int n = d.n, A = d.A, E = d.E, R = d.R, NH = d.NH;
@@ -134,7 +160,7 @@ __global__ __launch_bounds__(256) void mix_kernel(Dims d, Rep rp, const float* _
     const int64_t slot = ep * d.t_stride + t;
     mask = (float)rp.filled[slot];
     if (t > 0) mask *= 1.0f - (float)rp.term[slot - 1];   // q_learner.py:42-43
-    rew = rp.reward[slot];
+    rew = reward_of<RSV>(rp, RS, slot, m);
     term = (float)rp.term[slot];
   }
   [[maybe_unused]] const float wb = per_weight<PER>(W, valid, b);   // in flight with every other load
@@ -389,9 +415,10 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
                          const Lay& L, const Work& w, int32_t* curmax_out, int m, int lane, const float* hon,
                          const float* htg, MixScratch<MN>& sc, float* red_slot, float* v2_slot,
                          float* __restrict__ YT, const float* __restrict__ G, const float* __restrict__ W = nullptr,
-                         float* __restrict__ TDA = nullptr) {
+                         float* __restrict__ TDA = nullptr, const float* __restrict__ RS = nullptr) {
   constexpr int MODE = mix_pass(FULL);
   constexpr bool PER = (FULL & MIX_PER) != 0;
+  constexpr bool RSV = (FULL & MIX_RS) != 0;
   constexpr bool ONLINE = MODE != MIX_LAMBDA_TARGETS;   // chosen values, online mix, loss, mixer backward
   constexpr bool TARGET = MODE != MIX_LAMBDA_LOSS;      // double-Q selection and the target-side mix
   const int n = d.n, A = d.A, E = d.E, R = d.R, NH = d.NH;
@@ -453,7 +480,7 @@ MQ_DEV void mix_fast_row(const Dims& d, const Rep& rp, const float* __restrict__
   if (ONLINE && valid) {
     mask = (float)rp.filled[slot];
     if (t > 0) mask *= 1.0f - (float)rp.term[slot - 1];   // q_learner.py:42-43
-    rew = rp.reward[slot];
+    rew = reward_of<RSV>(rp, RS, slot, m);
     term = (float)rp.term[slot];
   }
   const float v2b0 = (ONLINE && qmix) ? P0[L.o[MQ_P_V2_B]] : 0.0f, v2b1 = (TARGET && qmix) ? P1[L.o[MQ_P_V2_B]] : 0.0f;
@@ -623,7 +650,8 @@ __global__ __launch_bounds__(256) void mix_fast_kernel(Dims d, Rep rp, const flo
   const float* G = nullptr;
   const float* W = nullptr;
   float* TDA = nullptr;
-  tail_args(YT, G, W, TDA, lam...);
+  const float* RS = nullptr;
+  tail_args_rs<(FULL & MIX_RS) != 0>(YT, G, W, TDA, RS, lam...);
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + wv;
   const int E = d.E, NH = d.NH;
@@ -634,7 +662,7 @@ __global__ __launch_bounds__(256) void mix_fast_kernel(Dims d, Rep rp, const flo
   const float* hon = w.HYP + (int64_t)m * NH;
   const float* htg = w.HYP + ((int64_t)d.M + m) * NH;
   mix_fast_row<MA, MN, FULL>(d, rp, P0, P1, L, w, curmax_out, m, lane, hon, htg, sc[wv], red[wv], v2red[wv], YT, G, W,
-                             TDA);
+                             TDA, RS);
   if constexpr (MODE == MIX_LAMBDA_TARGETS) return;   // no loss terms in this pass
   __syncthreads();
   if (threadIdx.x < 8) {

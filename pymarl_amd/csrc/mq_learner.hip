@@ -19,6 +19,9 @@
 //   reduce   deterministic two-pass slab sums -> flat gradient buffer (+ loss sums), per-block sums of squares
 //   --- (data-parallel all-reduce of the gradient buffer happens here, in the caller)
 //   apply    / sum(mask), clip_grad_norm_, RMSprop (mq_set_adam: Adam, apply_adam_kernel)
+//            (soft target updates, mq_set_soft_target: soft_update_kernel as the step's last launch)
+// Reward standardisation (mq_set_reward_norm): reward_norm_kernel ahead of `mix`, whose one-step pass and TD(lambda)
+// scan then read its output in place of the storage's rewards (epymarl_kernels.hpp).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -38,6 +41,7 @@
 #include "mix_kernels.hpp"
 #include "td_lambda_kernel.hpp"
 #include "per_kernels.hpp"
+#include "epymarl_kernels.hpp"
 #include "hyper_kernel.hpp"
 #include "hyper2_kernels.hpp"
 #include "dwh_kernel.hpp"
@@ -160,6 +164,15 @@ struct mq_handle {
   bool adam = false;
   mq_adam ad{};
   int64_t adam_step = 0;
+  // soft target updates (mq_set_soft_target): soft_update_kernel behind the apply, target = target omt + online tau
+  bool soft = false;
+  float soft_omt = 0.0f, soft_tau = 0.0f;
+  int last_soft = -1;   // of the last mq_apply (mq_last_soft_target)
+  // reward standardisation (mq_set_reward_norm): the caller's [mean, var, count] doubles, and RS [max_seq * max_batch],
+  // the step's standardised rewards, allocated by the first mq_set_reward_norm
+  double* rew_state = nullptr;
+  float* RS = nullptr;
+  bool have_rs = false;   // the last step standardised (mq_copy_intermediate 8, mq_last_reward_norm)
   int num_cu = 0;
   // timing: a ring of `slots` steps x PH_N (start, stop) event pairs; phases outside `mask` are not recorded
   int slots = 0;
@@ -265,6 +278,13 @@ AdamHP make_adam_hp(float lr, float beta1, float beta2, float eps, float wd, int
 int adam_blocks(const float* p, const float* g, const float* m, const float* v, int64_t n) {
   const uintptr_t a = (uintptr_t)p & 15;
   const bool same = ((uintptr_t)g & 15) == a && ((uintptr_t)m & 15) == a && ((uintptr_t)v & 15) == a;
+  const int64_t items = same ? n / 4 + 6 : n;
+  return (int)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, 1024));
+}
+
+// soft_update_kernel's grid, by the same rule
+int soft_blocks(const float* tg, const float* on, int64_t n) {
+  const bool same = ((uintptr_t)tg & 15) == ((uintptr_t)on & 15);
   const int64_t items = same ? n / 4 + 6 : n;
   return (int)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, 1024));
 }
@@ -429,6 +449,27 @@ void launch_mix_per(int mix, int nblk, const mq_handle* h, const Dims& d, const 
   }
 }
 
+// The one-step pass reading the standardised rewards (MIX_RS; PER: its PER form too): RS leads the trailing arguments.
+template <int FULL, typename... X>
+void launch_mix_rs(int mix, int nblk, const mq_handle* h, const Dims& d, const Rep& rp, const Lay& L, const Work& w,
+                   int32_t* curmax, hipStream_t s, X... x) {
+  const dim3 grid(nblk), block(256);
+  const float *P0 = h->on, *P1 = h->tg;
+  const float* RS = h->RS;
+  if (mix == MQ_MIX_FAST16)
+    hipLaunchKernelGGL((mix_fast_kernel<16, 16, FULL, const float*, X...>), grid, block, 0, s, d, rp, P0, P1, L, w,
+                       curmax, RS, x...);
+  else if (mix == MQ_MIX_FAST32)
+    hipLaunchKernelGGL((mix_fast_kernel<32, 16, FULL, const float*, X...>), grid, block, 0, s, d, rp, P0, P1, L, w,
+                       curmax, RS, x...);
+  else if (mix == MQ_MIX_STREAM)
+    hipLaunchKernelGGL((mix_kernel<true, FULL, const float*, X...>), grid, block, 0, s, d, rp, P0, P1, L, w, curmax,
+                       RS, x...);
+  else
+    hipLaunchKernelGGL((mix_kernel<false, FULL, const float*, X...>), grid, block, 0, s, d, rp, P0, P1, L, w, curmax,
+                       RS, x...);
+}
+
 // Plan the slab reductions of one step: regions in gradient order, then the loss sums (not part of the norm).
 struct RedBuilder {
   RedPlan pl{};
@@ -505,6 +546,7 @@ struct Step {
   int32_t* curmax;
   hipStream_t s;
   PhaseTimer pt;
+  const bool rnorm = false;   // reward standardisation is set (mq_set_reward_norm)
   const int64_t RT = (int64_t)d.Tp * d.R;
 
   int forward(const StepPlan& p);
@@ -614,8 +656,16 @@ int Step::hypernet(const StepPlan& p) {
 int Step::mixer_tail(const StepPlan& p) {
   const mq_config& c = h->cfg;
   pt.begin(PH_MIX);
+  if (rnorm) {   // the batch's rewards into the running statistics, and RS: the rewards every launch below reads
+    hipLaunchKernelGGL(reward_norm_kernel, dim3(1), dim3(RN_THREADS), 0, s, d, rp, h->rew_state, h->RS);
+    MQ_HIP(hipGetLastError());
+  }
   if (!p.lambda) {
-    if (p.per) launch_mix_per<MIX_ONE_STEP>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
+    if (rnorm && p.per)
+      launch_mix_rs<MIX_ONE_STEP | MIX_PER | MIX_RS>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s, h->per.weights,
+                                                     h->TDA);
+    else if (rnorm) launch_mix_rs<MIX_ONE_STEP | MIX_RS>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
+    else if (p.per) launch_mix_per<MIX_ONE_STEP>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
     else launch_mix<MIX_ONE_STEP>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
     MQ_HIP(hipGetLastError());
   } else {
@@ -627,7 +677,13 @@ int Step::mixer_tail(const StepPlan& p) {
     MQ_HIP(hipGetLastError());
     const float lg = (float)((double)c.td_lambda * (double)c.gamma);
     const float og = (float)((1.0 - (double)c.td_lambda) * (double)c.gamma);
-    hipLaunchKernelGGL(td_lambda_kernel, dim3(d.B), dim3(256), dyn, s, d, rp, (const float*)h->YT, h->G, k, lg, og);
+    if (rnorm) {
+      MQ_LDS(td_lambda_rs_kernel, dyn);
+      hipLaunchKernelGGL(td_lambda_rs_kernel, dim3(d.B), dim3(256), dyn, s, d, rp, (const float*)h->YT, h->G, k, lg, og,
+                         (const float*)h->RS);
+    } else {
+      hipLaunchKernelGGL(td_lambda_kernel, dim3(d.B), dim3(256), dyn, s, d, rp, (const float*)h->YT, h->G, k, lg, og);
+    }
     MQ_HIP(hipGetLastError());
     if (p.per) launch_mix_per<MIX_LAMBDA_LOSS>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
     else launch_mix<MIX_LAMBDA_LOSS>(p.mix, p.nblk_mix, h, d, rp, L, w, curmax, s);
@@ -900,6 +956,7 @@ int mq_destroy(mq_handle* h) {
   if (h->ws) (void)hipFree(h->ws);
   if (h->YT) (void)hipFree(h->YT);
   if (h->TDA) (void)hipFree(h->TDA);
+  if (h->RS) (void)hipFree(h->RS);
   if (h->A1) (void)hipFree(h->A1);
   if (h->comm && h->comm_owned) (void)ncclCommDestroy(h->comm);
   delete h;
@@ -951,8 +1008,12 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
     if (batch->n_episodes > h->per.n_prio)
       return set_err(MQ_ERR_ARG, "mq_per.n_prio is smaller than the replay's n_episodes");
   }
+  const bool rnorm = h->rew_state != nullptr;
+  if (rnorm && (h->comm || h->dp))
+    return set_err(MQ_ERR_ARG, "reward standardisation does not support data parallelism (a communicator is attached "
+                               "or mq_set_data_parallel is on): each rank would see only its shard's rewards");
   Step st{h, make_dims(h, batch), make_rep(batch), make_lay(h), h->w, h->curmax_user ? h->curmax_user : h->curmax_ws,
-          s, PhaseTimer{h, s}};
+          s, PhaseTimer{h, s}, rnorm};
   // a handle with the TD(lambda) workspace runs the lambda passes: cfg.td_lambda > 0 or MQ_PLAN lambda_path=1
   const StepPlan p = plan_step(h->cfg, h->ov, st.d, st.rp.nids > 0, h->YT != nullptr, device_cus(h), per,
                                  h->hyper2 ? 2 : 1);
@@ -971,6 +1032,7 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
   h->have_lambda = p.lambda;
   h->have_per = p.per;
   h->have_h2 = p.hyper2;
+  h->have_rs = rnorm;
   h->hyper_layers = p.hyper_layers;
   return MQ_OK;
 }
@@ -1002,10 +1064,66 @@ int mq_apply(mq_handle* h, void* stream) {
                        (const float*)h->w.norm_part, h->n_norm_part, hp, h->stats, (const int*)nullptr);
     MQ_HIP(hipGetLastError());
   }
+  if (h->soft) {   // the step's last launch: the targets follow the parameters the apply just wrote
+    hipLaunchKernelGGL(soft_update_kernel, dim3(soft_blocks(h->tg, h->on, h->P)), dim3(256), 0, s, h->tg,
+                       (const float*)h->on, h->P, h->soft_omt, h->soft_tau, (const int*)nullptr);
+    MQ_HIP(hipGetLastError());
+  }
+  h->last_soft = h->soft ? 1 : 0;
   pt.end();
   ++h->tstep;
   return MQ_OK;
 }
+
+int mq_set_soft_target(mq_handle* h, double tau) {
+  if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
+  if (tau == 0.0) {
+    h->soft = false;
+    h->soft_omt = h->soft_tau = 0.0f;
+    return MQ_OK;
+  }
+  if (!(tau > 0.0 && tau <= 1.0)) return set_err(MQ_ERR_ARG, "mq_set_soft_target: tau must be in (0, 1] (0: off)");
+  h->soft_omt = (float)(1.0 - tau);
+  h->soft_tau = (float)tau;
+  h->soft = true;
+  return MQ_OK;
+}
+
+int32_t mq_last_soft_target(const mq_handle* h) { return h ? h->last_soft : -1; }
+
+int mq_soft_update(float* target, const float* online, int64_t n, float one_minus_tau, float tau, void* stream) {
+  if (!target || !online) return set_err(MQ_ERR_ARG, "NULL pointer in mq_soft_update");
+  if (((uintptr_t)target | (uintptr_t)online) & 3)
+    return set_err(MQ_ERR_ARG, "mq_soft_update: a pointer is not aligned to a float");
+  if (n < 0) return set_err(MQ_ERR_ARG, "mq_soft_update: n must be >= 0");
+  if (!(tau > 0.0f && tau <= 1.0f)) return set_err(MQ_ERR_ARG, "mq_soft_update: tau must be in (0, 1]");
+  if (n == 0) return MQ_OK;
+  hipLaunchKernelGGL(soft_update_kernel, dim3(soft_blocks(target, online, n)), dim3(256), 0, (hipStream_t)stream,
+                     target, online, n, one_minus_tau, tau, (const int*)nullptr);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+int mq_set_reward_norm(mq_handle* h, double* state) {
+  if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
+  if (!state) {
+    h->rew_state = nullptr;
+    return MQ_OK;
+  }
+  if ((uintptr_t)state & 7) return set_err(MQ_ERR_ARG, "mq_set_reward_norm: state is not aligned to a double");
+  if (!h->RS) {
+    const int64_t len = align_up((int64_t)h->cfg.max_seq * h->cfg.max_batch);
+    const hipError_t e = hipMalloc((void**)&h->RS, len * sizeof(float));
+    if (e != hipSuccess) {
+      h->RS = nullptr;
+      return set_err(MQ_ERR_HIP, std::string("reward-standardisation workspace hipMalloc: ") + hipGetErrorString(e));
+    }
+  }
+  h->rew_state = state;
+  return MQ_OK;
+}
+
+int32_t mq_last_reward_norm(const mq_handle* h) { return h && h->have_fb ? (h->have_rs ? 1 : 0) : -1; }
 
 int mq_set_adam(mq_handle* h, const mq_adam* a) {
   if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
@@ -1191,6 +1309,11 @@ int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, vo
     case 6:
       if (!h->have_per) return set_err(MQ_ERR_STATE, "the last step was not a prioritized-replay step");
       src = h->TDA;
+      cnt = (int64_t)d.T * d.B;
+      break;
+    case 8:
+      if (!h->have_rs) return set_err(MQ_ERR_STATE, "the last step did not standardise the rewards");
+      src = h->RS;
       cnt = (int64_t)d.T * d.B;
       break;
     case 7: {   // the online net's first 2 He columns of A1's rows (row pitch N1)

@@ -64,4 +64,46 @@ __global__ __launch_bounds__(256) void td_lambda_kernel(Dims d, Rep rp, const fl
   }
 }
 
+// The same scan over standardised rewards (mq_set_reward_norm): r_t is RS[t][b], what reward_norm_kernel
+// (epymarl_kernels.hpp) wrote, not the storage's reward; everything else is td_lambda_kernel's, line for line. It is a
+// kernel of its own, not a shared inlined body: with the body shared, td_lambda_kernel's instruction schedule changed,
+// and the default path's device code is held identical from commit to commit (scripts/compare_device_code.py).
+__global__ __launch_bounds__(256) void td_lambda_rs_kernel(Dims d, Rep rp, const float* __restrict__ YT,
+                                                           float* __restrict__ G, int k, float lg, float og,
+                                                           const float* __restrict__ RS) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) float lam_sm[];
+  const int b = blockIdx.x, L = d.T, B = d.B;
+  float* yq = lam_sm;        // [L][k]
+  float* rw = yq + L * k;    // [L]
+  float* om = rw + L;        // [L] 1 - terminated
+  float* mk = om + L;        // [L] mask
+  const int64_t e0 = rp.ep(b) * d.t_stride;
+  for (int e = threadIdx.x; e < L * k; e += 256) {
+    const int t = e / k, j = e - t * k;
+    yq[e] = YT[((int64_t)t * B + b) * k + j];
+  }
+  for (int t = threadIdx.x; t < L; t += 256) {
+    rw[t] = RS[(int64_t)t * B + b];
+    om[t] = 1.0f - (float)rp.term[e0 + t];
+    float m = (float)rp.filled[e0 + t];
+    if (t > 0) m *= 1.0f - (float)rp.term[e0 + t - 1];   // q_learner.py:42-43
+    mk[t] = m;
+  }
+  __syncthreads();
+  const int j = threadIdx.x;
+  if (j >= k) return;
+  float tsum = 0.0f;
+  for (int t = 0; t < L; ++t) tsum += 1.0f - om[t];
+  float ret = yq[(L - 1) * k + j] * (1.0f - tsum);
+  float* out = G + (int64_t)b * k + j;
+  for (int t = L - 1; t >= 0; --t) {
+    const float boot = (og * yq[t * k + j]) * om[t];
+    const float inner = rw[t] + boot;
+    const float carry = lg * ret;
+    ret = carry + mk[t] * inner;
+    out[(int64_t)t * B * k] = ret;
+  }
+}
+
 }  // namespace mq

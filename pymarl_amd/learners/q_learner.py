@@ -10,6 +10,12 @@ Opt-in `optimizer: adam` (pymarl2's key; `weight_decay`, `adam_betas`, `adam_eps
 torch.optim.Adam's update (apply_adam_kernel, mq_set_adam) and `self.optimiser` a real torch.optim.Adam whose exp_avg /
 exp_avg_sq are views into two flat buffers, so opt.th has torch's format both ways. Without the key nothing changes.
 
+Opt-in epymarl keys (target_update_config, reward_norm_config): `target_update_interval_or_tau` above 1 is a hard target
+update counted in training steps, at most 1 a Polyak update after every step (soft_update_kernel, mq_set_soft_target:
+the step's last launch); `standardise_rewards: True` standardises the rewards with running statistics kept on the
+device (`self.rew_ms`, reward_norm_kernel, mq_set_reward_norm) before the target is formed. Without the keys nothing
+changes.
+
 Data parallel: with `args.learner_dp = True` and torch.distributed initialised (RCCL, one process
 per GPU), every rank calls train() with the SAME GLOBAL sample, as run.py:207-219 does unchanged (ranks share the
 seed, so the sampled ids agree; ids and contents checked on a call-count schedule, `args.learner_dp_check`); the
@@ -24,6 +30,8 @@ from __future__ import annotations
 
 import copy
 import ctypes
+import numbers
+import os
 
 import numpy as np
 
@@ -105,6 +113,41 @@ def optimizer_config(args):
     if not wd >= 0.0:
         raise ValueError("weight_decay must be >= 0, got {}.".format(wd))
     return name, dict(lr=args.lr, betas=betas, eps=eps, weight_decay=wd)
+
+
+def target_update_config(args):
+    """epymarl's target_update_interval_or_tau: (mode, value). Key absent or None: (None, None), the reference's
+    episode-counted target_update_interval applies. v > 1: ("hard", v), a hard update every v TRAINING STEPS
+    (target_update_interval is then ignored). 0 < v <= 1: ("soft", v), a Polyak update with tau = v after every step.
+    v <= 0, NaN or not a number (a bool is not one): ValueError."""
+    v = getattr(args, "target_update_interval_or_tau", None)
+    if v is None:
+        return None, None
+    if isinstance(v, bool) or not isinstance(v, numbers.Real):
+        raise ValueError("target_update_interval_or_tau must be a number, got {!r}.".format(v))
+    v = float(v)
+    if not v > 0.0:   # NaN too
+        raise ValueError("target_update_interval_or_tau must be > 0 (above 1: a hard update every that many training "
+                         "steps; at most 1: the soft update's tau), got {}.".format(v))
+    return ("hard", v) if v > 1.0 else ("soft", v)
+
+
+def reward_norm_config(args):
+    """epymarl's standardise_rewards: True standardises the rewards with running statistics before the TD target is
+    formed. Key absent: False (epymarl's own default is True: its configs carry the key). Not a bool: ValueError; with
+    learner_dp: ValueError (each rank would see only its shard's rewards)."""
+    v = getattr(args, "standardise_rewards", False)
+    if v is None:
+        return False
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError("standardise_rewards must be True or False, got {!r}.".format(v))
+    if v and getattr(args, "learner_dp", False):
+        raise ValueError("learner_dp is not supported with standardise_rewards: the running reward statistics belong "
+                         "to one device's batches, and each rank would see only its shard")
+    return bool(v)
+
+
+REW_MS_INIT = (0.0, 1.0, 1e-4)   # running (mean, var, count) of a fresh learner, epymarl's RunningMeanStd
 
 
 def is_per_batch(batch):
@@ -198,6 +241,11 @@ class QLearner:
         self.logger = logger
         self.params = list(mac.parameters())
         self.last_target_update_episode = 0
+        # epymarl's keys, both opt-ins: the target schedule in training steps (or soft), and reward standardisation
+        self.target_mode, self.target_value = target_update_config(args)
+        self.standardise_rewards = reward_norm_config(args)
+        self.training_steps = 0
+        self.last_target_update_step = 0
         self.mixer = None
         if args.mixer is not None:
             if args.mixer == "vdn":
@@ -231,6 +279,8 @@ class QLearner:
         dev = self.mac.agent.fc1.weight.device
         self._online, self.n_params = pack(self._mods, device=dev)
         self._target, _ = pack(self._tmods, device=dev)
+        # the running reward statistics [mean, var, count]: float64 on the device, never read by a step
+        self.rew_ms = th.tensor(REW_MS_INIT, dtype=th.float64, device=dev) if self.standardise_rewards else None
         self._alloc_state(dev)
         self._handle = None
         self._handle_key = None
@@ -309,6 +359,12 @@ class QLearner:
                 ad = _lib.MQAdam(exp_avg=self._m.data_ptr(), beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"],
                                  weight_decay=g["weight_decay"], step=self._opt_steps)
                 _lib.check(h.lib.mq_set_adam(h.h, ctypes.byref(ad)))
+            # sticky per handle, so a handle rebuilt for a larger batch gets them again (the statistics are the
+            # learner's tensor: they carry over)
+            if getattr(self, "target_mode", None) == "soft":
+                _lib.check(h.lib.mq_set_soft_target(h.h, self.target_value))
+            if getattr(self, "rew_ms", None) is not None:
+                _lib.check(h.lib.mq_set_reward_norm(h.h, _lib.ptr(self.rew_ms)))
             h.dp_on = False
             h.native = False
             if self._dp_active() and native_comm_wanted(self._online.device):
@@ -330,6 +386,9 @@ class QLearner:
         if per and (self.dp or getattr(self, "force_dp_norm", False)):
             raise ValueError("learner_dp is not supported with a PrioritizedReplayBuffer batch: the priorities and "
                              "importance weights belong to one device's buffer")
+        if getattr(self, "rew_ms", None) is not None and (self.dp or getattr(self, "force_dp_norm", False)):
+            raise ValueError("learner_dp is not supported with standardise_rewards: the running reward statistics "
+                             "belong to one device's batches, and each rank would see only its shard")
         if dp:
             batch = self._local_batch(batch)
         h = self._get_handle(batch)
@@ -358,9 +417,7 @@ class QLearner:
         self._last_batch = (batch.batch_size, rep.t_len)
         del keep
 
-        if (episode_num - self.last_target_update_episode) / self.args.target_update_interval >= 1.0:
-            self._update_targets()
-            self.last_target_update_episode = episode_num
+        self._target_schedule(episode_num)
 
         if t_env - self.log_stats_t >= self.args.learner_log_interval:
             st = self._stats.tolist()
@@ -370,6 +427,20 @@ class QLearner:
             self.logger.log_stat("q_taken_mean", st[3], t_env)
             self.logger.log_stat("target_mean", st[4], t_env)
             self.log_stats_t = t_env
+
+    def _target_schedule(self, episode_num):
+        """After the optimiser step of every train(): count it, then the hard target update when it is due."""
+        self.training_steps += 1
+        if self.target_mode is None:
+            if (episode_num - self.last_target_update_episode) / self.args.target_update_interval >= 1.0:
+                self._update_targets()
+                self.last_target_update_episode = episode_num
+        elif self.target_mode == "hard":
+            # epymarl's schedule: counted in training steps; target_update_interval is ignored
+            if (self.training_steps - self.last_target_update_step) / self.target_value >= 1.0:
+                self._update_targets()
+                self.last_target_update_step = self.training_steps
+        # "soft": the step's last launch already moved the targets (mq_set_soft_target); nothing to do or to print
 
     def _update_targets(self):
         if self._online.is_cuda and self._handle is not None:
@@ -388,7 +459,16 @@ class QLearner:
         if self._m is not None:
             self._m = self._m.to(dev)
         self._stats = self._stats.to(dev)
+        if self.rew_ms is not None:
+            self.rew_ms = self.rew_ms.to(dev)
         self._relink()
+
+    def reward_stats(self):
+        """The running reward statistics as a dict of Python floats: mean, var, count (synchronises)."""
+        if self.rew_ms is None:
+            raise _lib.MQError("reward_stats() needs standardise_rewards: True")
+        m, v, c = self.rew_ms.tolist()
+        return dict(mean=m, var=v, count=c)
 
     def save_models(self, path):
         self.mac.save_models(path)
@@ -399,6 +479,14 @@ class QLearner:
         sd = self.optimiser.state_dict()
         sd["state"] = {i: dict(v, step=v["step"].clone()) if "step" in v else v for i, v in sd["state"].items()}
         th.save(sd, "{}/opt.th".format(path))
+        # the epymarl keys' state, as plain dicts of Python numbers: the running reward statistics, and the counters
+        # of the step-counted target schedule
+        if self.rew_ms is not None:
+            th.save(self.reward_stats(), "{}/rew_ms.th".format(path))
+        if self.target_mode is not None:
+            th.save(dict(training_steps=int(self.training_steps),
+                         last_target_update_step=int(self.last_target_update_step)),
+                    "{}/target_update.th".format(path))
 
     def load_models(self, path):
         self.mac.load_models(path)
@@ -428,6 +516,22 @@ class QLearner:
             o += n
         steps = [float(self.optimiser.state[p]["step"]) for p in self.params if "step" in self.optimiser.state[p]]
         self._opt_steps = int(steps[0]) if steps else 0
+        if self.rew_ms is not None:
+            f = "{}/rew_ms.th".format(path)
+            if os.path.exists(f):
+                ms = th.load(f, map_location=ml, weights_only=True)
+                vals = [float(ms["mean"]), float(ms["var"]), float(ms["count"])]
+            else:   # a checkpoint written without standardise_rewards: start the statistics afresh, and say so
+                vals = list(REW_MS_INIT)
+                self.logger.console_logger.warning(
+                    "{} not found: standardise_rewards starts from fresh reward statistics".format(f))
+            self.rew_ms.copy_(th.tensor(vals, dtype=th.float64))
+        if self.target_mode is not None:
+            f = "{}/target_update.th".format(path)
+            if os.path.exists(f):
+                tu = th.load(f, map_location=ml, weights_only=True)
+                self.training_steps = int(tu["training_steps"])
+                self.last_target_update_step = int(tu["last_target_update_step"])
         self._relink()
 
     # -- extras (parity / diagnostics) -----------------------------------------------------------------------
@@ -449,11 +553,14 @@ class QLearner:
         inline_ids, hyper, mix, tiles, dwh (where QMIX's dW_hyper ran: "red1" or "bptt_grid"), td_lambda (1: the
         mixer tail ran as the TD(lambda) passes), bwd_lean (1: the fused BPTT ran its lean per-step path), per (1: a
         prioritized-replay step: weighted loss, then the priority write-back), hyper_layers (2: the two-layer QMIX
-        hypernet ran as launches of its own, 1: the one-layer hypernet, 0: no QMIX mixer)."""
+        hypernet ran as launches of its own, 1: the one-layer hypernet, 0: no QMIX mixer), reward_norm (1: the step
+        standardised its rewards, standardise_rewards), soft_target (1: the step ended with the soft target update)."""
         pl = _lib.MQPlan()
         _lib.check(self._handle.lib.mq_last_plan(self._handle.h, ctypes.byref(pl)))
         d = pl.as_dict()
         d["hyper_layers"] = int(self._handle.lib.mq_last_hyper_layers(self._handle.h))   # an entry of its own
+        d["reward_norm"] = int(self._handle.lib.mq_last_reward_norm(self._handle.h))
+        d["soft_target"] = int(self._handle.lib.mq_last_soft_target(self._handle.h))
         d["hyper"] = _lib.HYP_NAMES[d["hyper"]]
         d["mix"] = _lib.MIX_NAMES[d["mix"]]
         d["dwh"] = ("red1", "bptt_grid")[d["dwh"]]
@@ -473,7 +580,8 @@ class QLearner:
         5: the lambda targets in the same shape. After a prioritized-replay step (last_plan()["per"] == 1): 6: the
         unweighted |td * mask| the priority write-back summed, as (B, T, 1) (no mixer: summed over the agents).
         After a step of the two-layer hypernet (last_plan()["hyper_layers"] == 2): 7: the online net's layer-1
-        pre-activations [hyper_w_1.0 | hyper_w_final.0] as (B, T, 2 * hypernet_embed)."""
+        pre-activations [hyper_w_1.0 | hyper_w_final.0] as (B, T, 2 * hypernet_embed). After a step that standardised
+        its rewards (last_plan()["reward_norm"] == 1): 8: the standardised rewards the step read, as (B, T, 1)."""
         B, Tp = self._last_batch
         n, A = self.args.n_agents, self.args.n_actions
         cnt = ctypes.c_int64()
@@ -485,7 +593,7 @@ class QLearner:
             return out.view(Tp, B, n, A).permute(1, 0, 2, 3)
         if which == 3:
             return out.view(Tp, B, n, -1).permute(1, 0, 2, 3)
-        if which in (4, 5, 6, 7):
+        if which in (4, 5, 6, 7, 8):
             return out.view(Tp - 1, B, -1).permute(1, 0, 2)
         return out.view(Tp - 1, B, n).permute(1, 0, 2)
 
