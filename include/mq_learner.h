@@ -59,8 +59,18 @@ enum { MQ_NSTATS = 8 };  /* loss, grad_norm, td_error_abs, q_taken_mean, target_
 enum {
   MQ_P_FC1_W, MQ_P_FC1_B, MQ_P_RNN_W_IH, MQ_P_RNN_W_HH, MQ_P_RNN_B_IH, MQ_P_RNN_B_HH, MQ_P_FC2_W, MQ_P_FC2_B,
   MQ_P_HW1_W, MQ_P_HW1_B, MQ_P_HWF_W, MQ_P_HWF_B, MQ_P_HB1_W, MQ_P_HB1_B, MQ_P_V0_W, MQ_P_V0_B, MQ_P_V2_W,
-  MQ_P_V2_B, MQ_P_HW1_W2, MQ_P_HW1_B2, MQ_P_HWF_W2, MQ_P_HWF_B2, MQ_P_COUNT
+  MQ_P_V2_B, MQ_P_HW1_W2, MQ_P_HW1_B2, MQ_P_HWF_W2, MQ_P_HWF_B2, MQ_P_FFN_W, MQ_P_FFN_B, MQ_P_COUNT
 };
+
+/* The agent's middle layer (mq_config.agent). MQ_AGENT_GRU: the reference's GRUCell (rnn_agent.py:20), the default and
+ * what a zeroed field selects. MQ_AGENT_FFN: epymarl's use_rnn: False, rnn = Linear(64, 64) followed by a ReLU,
+ *   x1 = relu(fc1(xin));  h = relu(rnn(x1));  q = fc2(h)
+ * with the incoming hidden state ignored. MQ_P_FFN_W / MQ_P_FFN_B are then rnn.weight [64][64] / rnn.bias [64], the
+ * buffer's order is fc1.weight, fc1.bias, rnn.weight, rnn.bias, fc2.weight, fc2.bias, <mixer>, and the four GRU
+ * entries MQ_P_RNN_* report offset = total (tensors of zero floats), as the absent hypernet entries do. With the GRU
+ * the two FFN entries report offset = total. They sit after MQ_P_HWF_B2 so that every earlier entry keeps its
+ * number. */
+enum { MQ_AGENT_GRU = 0, MQ_AGENT_FFN = 1 };
 
 typedef struct mq_config {
   int32_t n_agents, n_actions, obs_dim, state_dim;
@@ -87,6 +97,9 @@ typedef struct mq_config {
                                 MQ_ERR_ARG. Ignored without a QMIX mixer. */
   int32_t hypernet_embed;    /* width of the two-layer hypernet's hidden layer, 1 .. MQ_HYPERNET_EMBED_MAX (two layers
                                 only; outside: MQ_ERR_ARG) */
+  int32_t agent;             /* MQ_AGENT_*: 0 = the GRU agent (the reference; every kernel of that path runs as it
+                                always did), 1 = the feed-forward agent (epymarl's use_rnn: False). Anything else:
+                                MQ_ERR_ARG. */
 } mq_config;
 enum { MQ_HYPERNET_EMBED_MAX = 64 };
 
@@ -261,13 +274,17 @@ int mq_set_per(mq_handle* h, const mq_per* per);
  * After a step of the two-layer hypernet (mq_last_hyper_layers = 2; MQ_ERR_STATE otherwise): 7 = the online net's
  * first-layer pre-activations [hyper_w_1.0 | hyper_w_final.0] as [t][b][2 * hypernet_embed], t < t_len - 1.
  * After a step that standardised its rewards (mq_last_reward_norm = 1; MQ_ERR_STATE otherwise): 8 = the standardised
- * rewards the step read, as [t][b], t < t_len - 1. */
+ * rewards the step read, as [t][b], t < t_len - 1.
+ * After a step of the feed-forward agent (mq_last_agent bit 0; MQ_ERR_STATE otherwise): 9 = the online net's
+ * h = relu(rnn(x1)) as [t][b*n+a][64]. */
 int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, void* stream);
 
 /* BasicMAC.forward(ep_batch, t) for every episode of `batch`: h_in/h_out [batch*n][64] (h_in may equal
  * h_out), q_out [batch*n][n_actions]; which = 0 online params, 1 target params (MQ_ERR_STATE when none are bound).
  * MQ_ERR_ARG as mq_train_step gives it: a host id (ep_ids_host) outside [0, n_episodes), or a batch without ids
- * whose batch_size exceeds n_episodes. */
+ * whose batch_size exceeds n_episodes.
+ * On a feed-forward handle (MQ_AGENT_FFN) this and mq_agent_forward run the three layers in one launch, write
+ * h = relu(rnn(x1)) to h_out and never read h_in, which may be NULL. */
 int mq_mac_forward(mq_handle* h, const mq_replay* batch, int32_t t, const float* h_in, float* h_out,
                    float* q_out, int32_t which, void* stream);
 /* RNNAgent.forward(inputs, hidden) (rnn_agent.py:27-36) on given inputs [rows][input_dim]. */
@@ -323,6 +340,12 @@ int mq_last_plan(const mq_handle* h, mq_plan* out);
  * gradients); mq_plan.hyper then names layer 1's kernel and mq_plan.dwh is 0. 1: the one-layer hypernet. 0: no QMIX
  * mixer. -1: NULL handle, or no forward/backward has run. */
 int32_t mq_last_hyper_layers(const mq_handle* h);
+/* The agent of the last mq_forward_backward, an entry of its own like mq_last_hyper_layers (mq_plan keeps its size).
+ * -1: NULL handle, or no forward/backward has run. 0: the GRU agent ran. Otherwise a bit set: bit 0 = the feed-forward
+ * agent ran (fc1 / rnn / fc2 as GEMMs forward; dP2 and the fc2 gradients, then dP1, [dW_rnn | db_rnn] and dW1 as GEMMs
+ * backward: ffn_kernels.hpp); bits 1 and 2 are reserved for a fused forward / backward kernel (never set by this
+ * library). After such a step mq_plan.fused_fwd, rw_fwd, fused_bwd, rw_bwd, tiles, bwd_lean and dwh are all 0. */
+int32_t mq_last_agent(const mq_handle* h);
 
 /* Optional per-kernel HIP-event timing of train steps (bench / profiling): events bracket every phase whose bit
  * is set in phase_mask (bit i = phase i of mq_phase_names), in a ring of `slots` steps; slots = 0 turns it off. */

@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MQ_LEARNER_LIB", os.path.join(HERE, "lib", "libmq_learner.so"))
 
 MIXER_NONE, MIXER_VDN, MIXER_QMIX = 0, 1, 2
+AGENT_GRU, AGENT_FFN = 0, 1   # MQ_AGENT_*
 NSUMS = 8
 NSTATS = 8
 PARAM_NAMES = [
@@ -20,6 +21,8 @@ PARAM_NAMES = [
     "hyper_b_1.weight", "hyper_b_1.bias", "V.0.weight", "V.0.bias", "V.2.weight", "V.2.bias",
     # two-layer hypernet only (hypernet_layers: 2): the entries above then name hyper_w_1.0 / hyper_w_final.0
     "hyper_w_1.2.weight", "hyper_w_1.2.bias", "hyper_w_final.2.weight", "hyper_w_final.2.bias",
+    # feed-forward agent only (use_rnn: False): the four rnn.* entries above are then empty
+    "rnn.weight", "rnn.bias",
 ]
 P_COUNT = len(PARAM_NAMES)
 
@@ -30,7 +33,7 @@ EXPORTS = [
     "mq_greedy_actions", "mq_set_timing", "mq_phase_times", "mq_phase_names", "mq_set_data_parallel",
     "mq_last_plan", "mq_qmix_forward", "mq_qmix_forward2", "mq_last_hyper_layers", "mq_per_sample", "mq_set_per",
     "mq_set_adam", "mq_opt_step", "mq_adam_update", "mq_set_soft_target", "mq_last_soft_target", "mq_soft_update",
-    "mq_set_reward_norm", "mq_last_reward_norm",
+    "mq_set_reward_norm", "mq_last_reward_norm", "mq_last_agent",
     # include/mc_coma.h
     "mc_create", "mc_destroy", "mc_param_offsets", "mc_bind", "mc_train_step", "mc_update_targets", "mc_policy",
     "mc_copy_intermediate", "mc_set_timing", "mc_phase_times", "mc_last_critic_path", "mq_comm_unique_id", "mq_comm_attach",
@@ -58,6 +61,7 @@ class MQConfig(ctypes.Structure):
         ("optim_alpha", ctypes.c_float), ("optim_eps", ctypes.c_float), ("grad_norm_clip", ctypes.c_float),
         ("max_batch", ctypes.c_int32), ("max_seq", ctypes.c_int32), ("huber_delta", ctypes.c_float),
         ("td_lambda", ctypes.c_float), ("hypernet_layers", ctypes.c_int32), ("hypernet_embed", ctypes.c_int32),
+        ("agent", ctypes.c_int32),
     ]
 
 
@@ -165,6 +169,7 @@ def load(required=True):
         "mq_soft_update": ([vp, vp, i64, ctypes.c_float, ctypes.c_float, vp], ctypes.c_int),
         "mq_set_reward_norm": ([vp, vp], ctypes.c_int),
         "mq_last_reward_norm": ([vp], i32),
+        "mq_last_agent": ([vp], i32),
         "mc_critic_forward_workspace": ([ctypes.POINTER(MCConfig), i32, i32], i64),
         "mc_critic_forward": ([vp, ctypes.POINTER(MCConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp], ctypes.c_int),
         "mq_phase_times": ([vp, ctypes.POINTER(ctypes.c_float), i32, ctypes.POINTER(i32)], ctypes.c_int),

@@ -1,5 +1,8 @@
 """BasicMAC: parameter-shared multi-agent controller (reference: src/controllers/basic_controller.py:10-154).
 
+With `use_rnn: False` (the feed-forward agent) `hidden_states` is carried as before; it is then just the last
+step's `h = relu(rnn(x1))`, which the next step does not read.
+
 `forward(ep_batch, t)` is one fused HIP step (`mq_mac_forward`): it builds [obs_t | onehot(a_{t-1}) | onehot(id)]
 from the replay rows in-kernel (basic_controller.py:100-135) and runs fc1 -> GRUCell -> fc2 for every
 (episode, agent) row. For agent_output_type "pi_logits" (COMA) a second HIP kernel (`mc_policy`) applies the
@@ -16,6 +19,7 @@ import torch as th
 from .. import _lib
 from ..components.action_selectors import REGISTRY as action_REGISTRY
 from ..modules.agents import REGISTRY as agent_REGISTRY
+from ..modules.agents.rnn_agent import hidden_dim, use_rnn_config
 
 
 def _on_device(ep_batch):
@@ -29,6 +33,9 @@ class BasicMAC:
         input_shape = self._get_input_shape(scheme)
         self._build_agents(input_shape)
         self.agent_output_type = args.agent_output_type
+        if self.agent_output_type == "pi_logits" and not use_rnn_config(args):
+            raise ValueError("use_rnn: False is not supported with agent_output_type pi_logits (COMA's policy, "
+                             "mc_policy): COMA's actor is the GRU agent")
         self.action_selector = action_REGISTRY[args.action_selector](args)
         self.hidden_states = None
 
@@ -65,7 +72,7 @@ class BasicMAC:
             ep_view = ep_batch
         rep, keep = replay_view(ep_view)
         bs = ep_batch.batch_size
-        H = self.args.rnn_hidden_dim
+        H = hidden_dim(self.args)
         h_in = self.hidden_states.reshape(bs * self.n_agents, H).float().contiguous()
         _lib.require_gpu(h_in)
         h_out = th.empty_like(h_in)

@@ -19,6 +19,9 @@
 //   reduce   deterministic two-pass slab sums -> flat gradient buffer (+ loss sums), per-block sums of squares
 //   --- (data-parallel all-reduce of the gradient buffer happens here, in the caller)
 //   apply    / sum(mask), clip_grad_norm_, RMSprop (mq_set_adam: Adam, apply_adam_kernel)
+// The feed-forward agent (mq_config.agent = MQ_AGENT_FFN, ffn_kernels.hpp) has no recurrence: fc1 / rnn / fc2 are three
+// GEMMs forward (gi and gru_fwd are absent), and gru_bwd's place is taken by ffn_dp2_kernel (dP2 and the fc2 gradients),
+// dx1 by the dP1 GEMM, dw1 by [dW_rnn | db_rnn] and dW1; everything from `hyper` to `apply` is untouched.
 //            (soft target updates, mq_set_soft_target: soft_update_kernel as the step's last launch)
 // Reward standardisation (mq_set_reward_norm): reward_norm_kernel ahead of `mix`, whose one-step pass and TD(lambda)
 // scan then read its output in place of the storage's rewards (epymarl_kernels.hpp).
@@ -44,6 +47,7 @@
 #include "epymarl_kernels.hpp"
 #include "hyper_kernel.hpp"
 #include "hyper2_kernels.hpp"
+#include "ffn_kernels.hpp"
 #include "dwh_kernel.hpp"
 #include "optim_kernels.hpp"
 #include "module_fwd.hpp"
@@ -160,6 +164,8 @@ struct mq_handle {
   float *A1 = nullptr, *dA1 = nullptr;
   bool have_h2 = false;   // the last step ran it (mq_copy_intermediate 7)
   int hyper_layers = 0;   // of the last step (mq_last_hyper_layers)
+  bool ffn = false;       // cfg.agent = MQ_AGENT_FFN: the feed-forward agent
+  int last_agent = 0;     // of the last step (mq_last_agent)
   // Adam (mq_set_adam): mq_apply launches apply_adam_kernel with ad.exp_avg beside sq; adam_step counts the steps applied
   bool adam = false;
   mq_adam ad{};
@@ -192,17 +198,28 @@ void compute_layout(mq_handle* h) {
   sz[MQ_P_RNN_W_IH] = 3LL * Hd * Hd; sz[MQ_P_RNN_W_HH] = 3LL * Hd * Hd;
   sz[MQ_P_RNN_B_IH] = 3 * Hd; sz[MQ_P_RNN_B_HH] = 3 * Hd;
   sz[MQ_P_FC2_W] = (int64_t)A * Hd; sz[MQ_P_FC2_B] = A;
+  const bool ffn = c.agent == MQ_AGENT_FFN;
+  if (ffn) {   // rnn is Linear(64, 64): the GRU's four tensors are empty
+    sz[MQ_P_RNN_W_IH] = sz[MQ_P_RNN_W_HH] = sz[MQ_P_RNN_B_IH] = sz[MQ_P_RNN_B_HH] = 0;
+    sz[MQ_P_FFN_W] = (int64_t)Hd * Hd; sz[MQ_P_FFN_B] = Hd;
+  }
   // the buffer's order: the enum's, with the two-layer hypernet's second layers behind their first layers
-  // (parameters() order of upstream's QMixer); at one layer the second-layer entries are empty and come last
+  // (parameters() order of upstream's QMixer) and the feed-forward agent's rnn.weight / rnn.bias in the GRU tensors'
+  // place; the entries a configuration lacks are empty and come last
   int order[MQ_P_COUNT];
   int no = 0;
   for (int i = 0; i <= MQ_P_V2_B; ++i) {
+    if (ffn && i >= MQ_P_RNN_W_IH && i <= MQ_P_RNN_B_HH) continue;
     order[no++] = i;
+    if (ffn && i == MQ_P_FC1_B) { order[no++] = MQ_P_FFN_W; order[no++] = MQ_P_FFN_B; }
     if (h->hyper2 && i == MQ_P_HW1_B) { order[no++] = MQ_P_HW1_W2; order[no++] = MQ_P_HW1_B2; }
     if (h->hyper2 && i == MQ_P_HWF_B) { order[no++] = MQ_P_HWF_W2; order[no++] = MQ_P_HWF_B2; }
   }
   if (!h->hyper2)
-    for (int i = MQ_P_HW1_W2; i < MQ_P_COUNT; ++i) order[no++] = i;
+    for (int i = MQ_P_HW1_W2; i <= MQ_P_HWF_B2; ++i) order[no++] = i;
+  if (ffn)
+    for (int i = MQ_P_RNN_W_IH; i <= MQ_P_RNN_B_HH; ++i) order[no++] = i;
+  else { order[no++] = MQ_P_FFN_W; order[no++] = MQ_P_FFN_B; }
   if (c.mixer == MQ_MIXER_QMIX) {
     sz[MQ_P_HW1_W] = (int64_t)E * n * S; sz[MQ_P_HW1_B] = (int64_t)E * n;
     sz[MQ_P_HWF_W] = (int64_t)E * S; sz[MQ_P_HWF_B] = E;
@@ -228,7 +245,8 @@ void compute_layout(mq_handle* h) {
     y.hbw = h->off[MQ_P_HB1_W]; y.hbb = h->off[MQ_P_HB1_B]; y.v0w = h->off[MQ_P_V0_W]; y.v0b = h->off[MQ_P_V0_B];
     y.He = c.hypernet_embed; y.E = E; y.nE = n * E; y.N1 = 2 * y.He + 2 * E;
   }
-  h->len_rnn = h->off[MQ_P_FC2_B] + A - h->off[MQ_P_RNN_W_IH];
+  // the BPTT's slab: [w_ih | w_hh | b_ih | b_hh | fc2.w | fc2.b]; feed-forward agent: [rnn.w | rnn.b | fc2.w | fc2.b]
+  h->len_rnn = h->off[MQ_P_FC2_B] + A - h->off[ffn ? MQ_P_FFN_W : MQ_P_RNN_W_IH];
   h->pitch_rnn = (h->len_rnn + 3) & ~int64_t(3);
   h->len_mix = h->off[MQ_P_V2_W] - h->off[MQ_P_HW1_W];
 }
@@ -555,10 +573,31 @@ struct Step {
   int hypernet2_backward(const StepPlan& p);
   int bptt(const StepPlan& p);
   int reduce(const StepPlan& p);
+  // feed-forward agent: slab_rnn holds the step's [dWr | dbr] split-K slabs, then ffn_dp2_kernel's [dW2 | db2] slabs
+  static int64_t ffn_w2_slabs(const StepPlan& p) { return (int64_t)p.ffn_wr_ns * FfnDwrProb::LEN; }
 };
 
 int Step::forward(const StepPlan& p) {
   const float *P0 = h->on, *P1 = h->tg;
+  if (p.ffn) {
+    // the feed-forward agent: three row-parallel GEMMs, both nets each (ffn_kernels.hpp)
+    pt.begin(PH_FC1);
+    {
+      Fc1Prob p1{d, rp, h->on, h->tg, h->off[MQ_P_FC1_W], h->off[MQ_P_FC1_B], w.X1, w.XIN, RT};
+      MQ_HIP(launch_gemm(p1, (int)RT, 2 * mq::H, 1, s));
+    }
+    pt.begin(PH_GRUF);
+    {
+      FfnHidProb ph{w.X1, h->on, h->tg, h->off[MQ_P_FFN_W], h->off[MQ_P_FFN_B], w.Hs, RT};
+      MQ_HIP(launch_gemm(ph, (int)RT, mq::H, 2, s));
+    }
+    pt.begin(PH_FC2);
+    {
+      Fc2Prob p2{w.Hs, h->on, h->tg, h->off[MQ_P_FC2_W], h->off[MQ_P_FC2_B], w.Q, RT, d.A};
+      MQ_HIP(launch_gemm(p2, (int)RT, d.A, 2, s));
+    }
+    return MQ_OK;
+  }
   if (p.fwd == FWD_TILES) {
     // row tiles of 32 (two M-tiles) per workgroup, both nets: the recurrence and fc1 / W_ih / fc2 on MFMA
     pt.begin(PH_GRUF);
@@ -717,6 +756,27 @@ int Step::bptt(const StepPlan& p) {
   const float* P0 = h->on;
   const int64_t l1 = (int64_t)mq::H * d.I + mq::H;
   const size_t dyn = ((size_t)2 * d.A * mq::H + d.A) * sizeof(float);   // the one-row kernels' fc2 staging
+  if (p.ffn) {
+    // dP2 (in dGI's buffer, as [RT][H]) and the fc2-gradient slabs, then dP1, [dWr | dbr] and dW1 as GEMMs
+    const size_t dyn2 = ffn_dp2_lds_bytes(d.A);
+    MQ_LDS(ffn_dp2_kernel, dyn2);
+    hipLaunchKernelGGL(ffn_dp2_kernel, dim3(p.ffn_nblk2), dim3(256), dyn2, s, d, rp, P0 + h->off[MQ_P_FC2_W],
+                       (const float*)w.dch, (const float*)w.Hs, w.dGI, w.slab_rnn + ffn_w2_slabs(p), p.ffn_rpb);
+    MQ_HIP(hipGetLastError());
+    pt.begin(PH_DX1);
+    {
+      FfnDx1Prob px{w.dGI, P0 + h->off[MQ_P_FFN_W], w.X1, w.dP1, RT};
+      MQ_HIP(launch_gemm(px, (int)RT, mq::H, 1, s));
+    }
+    pt.begin(PH_DW1);
+    {
+      FfnDwrProb pr{w.dGI, w.X1, w.slab_rnn, RT, p.ffn_wr_ns};
+      MQ_HIP(launch_gemm(pr, mq::H, mq::H, p.ffn_wr_ns, s));
+      Dw1Prob p1{d.I, w.dP1, w.XIN, w.slab_fc1, RT, p.dw1_ns};
+      MQ_HIP(launch_gemm(p1, mq::H, d.I, p.dw1_ns, s));
+    }
+    return MQ_OK;
+  }
   if (p.fwd == FWD_TILES) {
     // the two-role (chain / weight-gradient waves) BPTT, 512 threads
     dispatch_kq1(p.kq1, [&](auto K) {
@@ -784,7 +844,10 @@ int Step::reduce(const StepPlan& p) {
   const bool qmix = h->cfg.mixer == MQ_MIXER_QMIX;
   RedBuilder rb(w.red_tmp);
   rb.add(w.slab_fc1, p.nsplit_fc1, (int64_t)mq::H * d.I + mq::H, h->grad + h->off[MQ_P_FC1_W], true);
-  if (p.fused_bwd) {   // [W_ih | W_hh] in the BPTT's C-tile order (red_dst), then the biases and fc2
+  if (p.ffn) {   // [rnn.w | rnn.b] from the split-K slabs, [fc2.w | fc2.b] from ffn_dp2_kernel's
+    rb.add(w.slab_rnn, p.ffn_wr_ns, FfnDwrProb::LEN, h->grad + h->off[MQ_P_FFN_W], true);
+    rb.add(w.slab_rnn + ffn_w2_slabs(p), p.ffn_nblk2, (int64_t)d.A * mq::H + d.A, h->grad + h->off[MQ_P_FC2_W], true);
+  } else if (p.fused_bwd) {   // [W_ih | W_hh] in the BPTT's C-tile order (red_dst), then the biases and fc2
     const int64_t lm = 2LL * mq::G3 * mq::H;
     rb.add(w.slab_rnn, p.nblk_bwd, lm, h->grad + h->off[MQ_P_RNN_W_IH], true, h->pitch_rnn, false, 1);
     rb.add(w.slab_rnn + lm, p.nblk_bwd, h->len_rnn - lm, h->grad + h->off[MQ_P_RNN_W_IH] + lm, true, h->pitch_rnn);
@@ -820,6 +883,19 @@ int Step::reduce(const StepPlan& p) {
   return MQ_OK;
 }
 
+// One acting step of the feed-forward agent (mq_mac_forward / mq_agent_forward on an MQ_AGENT_FFN handle): the three
+// layers in one launch, h = relu(rnn(x1)) to h_out; the incoming hidden state is not read.
+int ffn_step(const mq_handle* h, const Dims& d, const Rep& rp, int32_t which, int t, const float* xin_dense, int rows,
+             float* h_out, float* q_out, hipStream_t s) {
+  const size_t smem = ffn_step_lds_bytes(d.I);
+  MQ_LDS(ffn_step_kernel, smem);
+  hipLaunchKernelGGL(ffn_step_kernel, dim3(rows), dim3(256), smem, s, d, rp, (const float*)(which ? h->tg : h->on),
+                     h->off[MQ_P_FC1_W], h->off[MQ_P_FC1_B], h->off[MQ_P_FFN_W], h->off[MQ_P_FFN_B],
+                     h->off[MQ_P_FC2_W], h->off[MQ_P_FC2_B], t, xin_dense, h_out, q_out);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -844,6 +920,8 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
     return set_err(MQ_ERR_ARG, "mixing_embed_dim must be in [1, 64]");
   if (c.mixer == MQ_MIXER_QMIX && (c.hypernet_layers < 0 || c.hypernet_layers > 2))
     return set_err(MQ_ERR_ARG, "hypernet_layers must be 1 or 2 (0: 1)");
+  if (c.agent != MQ_AGENT_GRU && c.agent != MQ_AGENT_FFN)
+    return set_err(MQ_ERR_ARG, "agent must be MQ_AGENT_GRU (0) or MQ_AGENT_FFN (1)");
   const bool hyper2 = c.mixer == MQ_MIXER_QMIX && c.hypernet_layers == 2;
   if (hyper2 && (c.hypernet_embed < 1 || c.hypernet_embed > MQ_HYPERNET_EMBED_MAX))
     return set_err(MQ_ERR_ARG, "hypernet_embed must be in [1, " + std::to_string((int)MQ_HYPERNET_EMBED_MAX) + "]");
@@ -863,6 +941,7 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
   h->cfg = c;
   h->ov = ov;
   h->hyper2 = hyper2;
+  h->ffn = c.agent == MQ_AGENT_FFN;
   const Dims dmax = mq::make_dims(c, c.max_batch, c.max_seq, c.max_seq);   // E, I, NH as every step derives them
   h->E = dmax.E; h->I = dmax.I; h->NH = dmax.NH;
   compute_layout(h);
@@ -875,7 +954,10 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
   const int64_t NH = h->NH;
   auto ng = [](int64_t ns) { return std::min<int64_t>(ns, kRedZ); };
   const int64_t nfc1 = std::max<int64_t>(kNsplitMax, Rm);   // fc1 slabs: split-K GEMM, or one per fused-BPTT row
-  const int64_t red_tmp = ng(Rm) * h->len_rnn + ng(nfc1) * (Hd * h->I + Hd) + ng(kNsplitMax) * h->len_mix +
+  // the feed-forward agent's slab_rnn, from the largest batch: its [dWr | dbr] slabs, then its [dW2 | db2] slabs
+  const int64_t ffn_ns = ffn_wr_ns_max(RT), ffn_nb = ffn_nblk2_max(RT);
+  const int64_t ffn_slabs = h->ffn ? ffn_ns * FfnDwrProb::LEN + ffn_nb * (A * Hd + A) : 0;
+  const int64_t red_tmp = (h->ffn ? ng(ffn_ns) * FfnDwrProb::LEN + ng(ffn_nb) * (A * Hd + A) : 0) + ng(Rm) * h->len_rnn + ng(nfc1) * (Hd * h->I + Hd) + ng(kNsplitMax) * h->len_mix +
                           ng(nmix) * (h->E + 1) + ng(nmix) * 8;
   const int64_t norm_parts = (Hd * h->I + Hd + 255) / 256 + (h->len_rnn + 255) / 256 + (h->len_mix + 255) / 256 +
                              (h->E + 1 + 255) / 256 + 1 + 8;
@@ -891,7 +973,7 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
       RT * 3 * Hd,                                   // dGI
       RT * Hd,                                       // dP1
       nfc1 * (Hd * h->I + Hd),                       // slab_fc1
-      Rm * h->pitch_rnn,                             // slab_rnn (RW = 1 worst case)
+      std::max(Rm * h->pitch_rnn, ffn_slabs),        // slab_rnn (RW = 1 worst case)
       (int64_t)kNsplitMax * h->len_mix,              // slab_mix
       nmix * (h->E + 1),                             // slab_v2
       nmix * 8,                                      // loss_part
@@ -1016,7 +1098,7 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
           s, PhaseTimer{h, s}, rnorm};
   // a handle with the TD(lambda) workspace runs the lambda passes: cfg.td_lambda > 0 or MQ_PLAN lambda_path=1
   const StepPlan p = plan_step(h->cfg, h->ov, st.d, st.rp.nids > 0, h->YT != nullptr, device_cus(h), per,
-                                 h->hyper2 ? 2 : 1);
+                                 h->hyper2 ? 2 : 1, h->cfg.agent);
   st.w.rec_coef = p.rec_coef;
   if ((rc = st.forward(p)) || (rc = st.hypernet(p)) || (rc = st.mixer_tail(p)) || (rc = st.hypernet2_backward(p)) ||
       (rc = st.bptt(p)) ||
@@ -1034,6 +1116,7 @@ static int fb_impl(mq_handle* h, const mq_replay* batch, hipStream_t s) {
   h->have_h2 = p.hyper2;
   h->have_rs = rnorm;
   h->hyper_layers = p.hyper_layers;
+  h->last_agent = p.agent_report;
   return MQ_OK;
 }
 
@@ -1173,6 +1256,8 @@ int mq_last_plan(const mq_handle* h, mq_plan* out) {
 }
 
 int32_t mq_last_hyper_layers(const mq_handle* h) { return h && h->have_fb ? h->hyper_layers : -1; }
+
+int32_t mq_last_agent(const mq_handle* h) { return h && h->have_fb ? h->last_agent : -1; }
 
 int mq_set_data_parallel(mq_handle* h, int32_t on) {
   if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
@@ -1316,6 +1401,11 @@ int mq_copy_intermediate(mq_handle* h, int which, float* dst, int64_t* count, vo
       src = h->RS;
       cnt = (int64_t)d.T * d.B;
       break;
+    case 9:
+      if (!(h->last_agent & 1)) return set_err(MQ_ERR_STATE, "the last step did not run the feed-forward agent");
+      src = h->w.Hs;
+      cnt = RT * mq::H;
+      break;
     case 7: {   // the online net's first 2 He columns of A1's rows (row pitch N1)
       if (!h->have_h2) return set_err(MQ_ERR_STATE, "the last step did not run the two-layer hypernet");
       const int64_t wd = 2 * h->y2.He;
@@ -1336,7 +1426,7 @@ int mq_mac_forward(mq_handle* h, const mq_replay* batch, int32_t t, const float*
                    int32_t which, void* stream) {
   if (!h || !h->on) return set_err(MQ_ERR_STATE, "mq_mac_forward before mq_bind");
   if (which && !h->tg) return set_err(MQ_ERR_STATE, "target parameters not bound");
-  if (!batch || !batch->obs || !batch->actions || !batch->filled || !h_in || !h_out || !q_out)
+  if (!batch || !batch->obs || !batch->actions || !batch->filled || (!h_in && !h->ffn) || !h_out || !q_out)
     return set_err(MQ_ERR_ARG, "NULL pointer in mq_mac_forward");
   if (t < 0 || t >= batch->t_stride) return set_err(MQ_ERR_ARG, "t outside the stored episode");
   if (batch->batch_size < 1) return set_err(MQ_ERR_ARG, "empty batch");
@@ -1346,6 +1436,7 @@ int mq_mac_forward(mq_handle* h, const mq_replay* batch, int32_t t, const float*
   const Dims d = make_dims(h, &b);
   const Rep rp = make_rep(batch);
   const Lay L = make_lay(h);
+  if (h->ffn) return ffn_step(h, d, rp, which, (int)t, nullptr, d.R, h_out, q_out, (hipStream_t)stream);
   const size_t smem = (size_t)(((d.I + 3) & ~3) + mq::H * 3 + mq::G3 * 2) * sizeof(float);
   hipLaunchKernelGGL(mac_step_kernel, dim3(d.R), dim3(256), smem, (hipStream_t)stream, d, rp,
                      (const float*)(which ? h->tg : h->on), L, (int)t, (const float*)nullptr, h_in, h_out, q_out);
@@ -1357,7 +1448,8 @@ int mq_agent_forward(mq_handle* h, const float* inputs, int32_t rows, const floa
                      int32_t which, void* stream) {
   if (!h || !h->on) return set_err(MQ_ERR_STATE, "mq_agent_forward before mq_bind");
   if (which && !h->tg) return set_err(MQ_ERR_STATE, "target parameters not bound");
-  if (!inputs || !h_in || !h_out || !q_out || rows < 0) return set_err(MQ_ERR_ARG, "bad mq_agent_forward args");
+  if (!inputs || (!h_in && !h->ffn) || !h_out || !q_out || rows < 0)
+    return set_err(MQ_ERR_ARG, "bad mq_agent_forward args");
   if (rows == 0) return MQ_OK;
   mq_replay b;
   std::memset(&b, 0, sizeof(b));
@@ -1366,6 +1458,7 @@ int mq_agent_forward(mq_handle* h, const float* inputs, int32_t rows, const floa
   d.n = 1;   // rows are independent here: block -> row, agent id unused
   const Rep rp = make_rep(&b);
   const Lay L = make_lay(h);
+  if (h->ffn) return ffn_step(h, d, rp, which, 0, inputs, rows, h_out, q_out, (hipStream_t)stream);
   const size_t smem = (size_t)(((d.I + 3) & ~3) + mq::H * 3 + mq::G3 * 2) * sizeof(float);
   hipLaunchKernelGGL(mac_step_kernel, dim3(rows), dim3(256), smem, (hipStream_t)stream, d, rp,
                      (const float*)(which ? h->tg : h->on), L, 0, inputs, h_in, h_out, q_out);

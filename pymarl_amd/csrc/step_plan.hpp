@@ -14,6 +14,7 @@
 #include "hyper_kernel.hpp"
 #include "dwh_kernel.hpp"
 #include "optim_kernels.hpp"
+#include "ffn_kernels.hpp"
 #include "switches.hpp"
 
 namespace mq {
@@ -52,6 +53,9 @@ struct PlanOverrides {
   // the TD(lambda) passes of the mixer tail (td_lambda_kernel.hpp) even at cfg.td_lambda = 0, where they compute the
   // one-step target through the scan
   bool lambda_path = false;
+  // feed-forward agent: the most workgroups of ffn_dp2_kernel (ffn_dp2_blocks=<n>, 1 .. kFfnDp2Blocks; 0: the default
+  // cap). Fewer workgroups walk longer runs of rows: the same sums in another slab partition (tests, A/B runs)
+  int ffn_dp2_blocks = 0;
 };
 
 // The one read of MQ_PLAN per handle (mq_create).
@@ -68,6 +72,7 @@ inline PlanOverrides read_plan_overrides() {
   o.pair_hyp_epi = plan_flag("pair_hyp_epi");
   o.mix_generic = plan_flag("mix_generic");
   o.lambda_path = plan_int("lambda_path", 0) != 0;
+  o.ffn_dp2_blocks = plan_int("ffn_dp2_blocks", 0);
   return o;
 }
 
@@ -139,14 +144,88 @@ struct StepPlan {
   int nblk_mix = 1;   // the mixer tail's workgroups: slab_v2 / loss_part slabs
   int nblk_bwd = 1;   // the BPTT's workgroups: slab_rnn slabs
   int nsplit_fc1 = 1, nsplit_mix = 1;   // slab_fc1 / slab_mix slabs
+  // the feed-forward agent (mq_config.agent = MQ_AGENT_FFN, ffn_kernels.hpp): the forward and the backward are the
+  // GEMM chain; fwd / fused_bwd / rw_* / lean above are then unused. ffn_wr_ns: split-K slices of [dWr | dbr];
+  // ffn_nblk2 workgroups of ffn_dp2_kernel own ffn_rpb rows each (the fc2-gradient slabs)
+  bool ffn = false;
+  int ffn_wr_ns = 1, ffn_nblk2 = 1, ffn_rpb = FFN_DP2_STEP;
+  int agent_report = 0;   // what mq_last_agent returns
   mq_plan report{};   // what mq_last_plan returns
 };
 
+// Split-K slices of a weight-gradient GEMM with `ntile` output tiles over RT rows: enough workgroups to fill the
+// device, every slice non-empty under krange_split's GBK rounding.
+inline int split_k_slices(int64_t RT, int ntile) {
+  int ns = (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RT / 256));
+  ns = std::max(1, std::min(ns, (512 + ntile - 1) / ntile));
+  const int64_t chunk = ((RT + ns - 1) / ns + GBK - 1) / GBK * GBK;
+  return (int)((RT + chunk - 1) / chunk);
+}
+
+// most workgroups (fc2-gradient slabs) of ffn_dp2_kernel: a workgroup walks its rows four at a time, each round a
+// dependent chain of loads (episode id -> action, dchosen, Hh), so the launch is as long as the longest walk. At the
+// cfg2 shape (30,976 rows) 1024 leave 8 rounds each (24 us; a cap of 256, 31 rounds, measured 40 us), and the slabs
+// of A * 65 floats are summed by reduction pass 1 in the launch it shares with dW_hyper
+constexpr int kFfnDp2Blocks = 1024;
+// Upper bounds of a handle's feed-forward slabs from its largest batch (mq_create's workspace): the [dWr | dbr]
+// split-K slices and ffn_dp2_kernel's workgroups of any step with at most RTmax rows.
+inline int ffn_wr_ns_max(int64_t RTmax) { return (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RTmax / 256)); }
+inline int ffn_nblk2_max(int64_t RTmax) {
+  return (int)std::min<int64_t>(kFfnDp2Blocks, (RTmax + FFN_DP2_STEP - 1) / FFN_DP2_STEP);
+}
+
+// The mixer tail's kernel (MQ_MIX_*): the same for either agent kind.
+inline int pick_mix(const Dims& d, const PlanOverrides& o) {
+  const bool fast = d.n <= 16 && d.E <= 64;   // mix_kernel serves the rest (n > 16 or A > 32)
+  const bool stream = mix_stream_ok(d.n, d.A) && !o.mix_generic;
+  return fast && d.A <= 16 ? MQ_MIX_FAST16 : fast && d.A <= 32 ? MQ_MIX_FAST32 : stream ? MQ_MIX_STREAM : MQ_MIX_GENERIC;
+}
+
 inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims& d, bool inline_ids,
-                          bool have_lambda_ws, int num_cu, bool per = false, int hyper_layers = 1) {
+                          bool have_lambda_ws, int num_cu, bool per = false, int hyper_layers = 1,
+                          int agent = MQ_AGENT_GRU) {
   StepPlan p;
   const int64_t RT = (int64_t)d.Tp * d.R;
   const bool qmix = c.mixer == MQ_MIXER_QMIX;
+  if (agent == MQ_AGENT_FFN) {
+    // No chain over t, so none of the recurrence's choices exists. The hypernet is a launch of its own, dW_hyper rides
+    // with reduction pass 1, and the mixer tail is chosen as for the GRU: it meets the agent through Q and dQ/dchosen.
+    const bool hyper2 = qmix && hyper_layers == 2;
+    p.ffn = true;
+    p.agent_report = 1;
+    if (qmix) {
+      p.hyp_place = HYP_OWN_LAUNCH;
+      p.hyper2 = hyper2;
+      p.hyper = hyper2 ? MQ_HYP_GEMM : hyper_ws_ok(d.S, d.E, d.NH, d.M) ? MQ_HYP_WS
+                : hyper_ok(d.S, d.NH) ? MQ_HYP_LDS : MQ_HYP_GEMM;
+      p.ns = p.nsplit_mix = std::max(1, std::min({o.dwh_split, kRedZ, (d.M + 1) / 2}));
+      if (!hyper2) {
+        p.dwh_in_red1 = true;
+        p.tj = (d.NH + DWH_T - 1) / DWH_T;
+        p.ts = (d.S + 1 + DWH_T - 1) / DWH_T;
+        p.ndwh = p.tj * p.ts * p.ns;
+      }
+    }
+    p.mix = pick_mix(d, o);
+    p.lambda = have_lambda_ws;
+    p.per = per;
+    p.nblk_mix = (d.M + 3) / 4;
+    p.dw1_ns = p.nsplit_fc1 = split_k_slices(RT, (d.I + Dw1Prob::BN - 1) / Dw1Prob::BN);
+    p.ffn_wr_ns = split_k_slices(RT, 1);
+    const int cap = o.ffn_dp2_blocks > 0 ? std::min(o.ffn_dp2_blocks, kFfnDp2Blocks) : kFfnDp2Blocks;
+    const int64_t per_blk = (RT + cap - 1) / cap;
+    p.ffn_rpb = (int)((per_blk + FFN_DP2_STEP - 1) / FFN_DP2_STEP * FFN_DP2_STEP);
+    p.ffn_nblk2 = (int)((RT + p.ffn_rpb - 1) / p.ffn_rpb);
+    mq_plan& r = p.report;   // fused_fwd, rw_fwd, fused_bwd, rw_bwd, tiles, bwd_lean and dwh stay 0
+    r.rows = d.R;
+    r.inline_ids = inline_ids ? 1 : 0;
+    r.hyper = p.hyper;
+    r.mix = p.mix;
+    r.td_lambda = p.lambda ? 1 : 0;
+    r.per = p.per ? 1 : 0;
+    p.hyper_layers = hyper2 ? 2 : qmix ? 1 : 0;
+    return p;
+  }
   // the two-layer hypernet never rides in a forward or in the BPTT's grid: the forward and BPTT choices below are then
   // those of a step without a hypernet (the same shape's VDN plan)
   const bool hyper2 = qmix && hyper_layers == 2;
@@ -195,10 +274,7 @@ inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims
   }
 
   // mixer tail
-  const bool fast = d.n <= 16 && d.E <= 64;   // mix_kernel serves the rest (n > 16 or A > 32)
-  const bool stream = mix_stream_ok(d.n, d.A) && !o.mix_generic;
-  p.mix = fast && d.A <= 16 ? MQ_MIX_FAST16 : fast && d.A <= 32 ? MQ_MIX_FAST32 : stream ? MQ_MIX_STREAM
-                                                                                        : MQ_MIX_GENERIC;
+  p.mix = pick_mix(d, o);
   p.lambda = have_lambda_ws;   // cfg.td_lambda > 0 or MQ_PLAN lambda_path=1 (mq_create)
   p.per = per;   // armed for this step (mq_set_per): changes no other choice
   p.nblk_mix = (d.M + 3) / 4;
@@ -210,12 +286,7 @@ inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims
     p.nblk_bwd = p.nsplit_fc1 = d.R;
   } else {
     p.nblk_bwd = (d.R + p.rw_bwd - 1) / p.rw_bwd;
-    const int ntile = (d.I + Dw1Prob::BN - 1) / Dw1Prob::BN;
-    int ns = (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RT / 256));
-    ns = std::max(1, std::min(ns, (512 + ntile - 1) / ntile));
-    // keep every split non-empty under krange_split's GBK rounding
-    const int64_t chunk = ((RT + ns - 1) / ns + GBK - 1) / GBK * GBK;
-    p.dw1_ns = p.nsplit_fc1 = (int)((RT + chunk - 1) / chunk);
+    p.dw1_ns = p.nsplit_fc1 = split_k_slices(RT, (d.I + Dw1Prob::BN - 1) / Dw1Prob::BN);
   }
 
   // dW_hyper: appended to the fused BPTT's grid when its rows exceed the CUs (the second wave of rows leaves CUs

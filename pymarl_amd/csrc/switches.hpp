@@ -4,8 +4,8 @@
 //            read_plan_overrides (step_plan.hpp) in mq_create, into the PlanOverrides that plan_step takes:
 //            unfused_fwd, unfused_bwd, row_tiles=0|1, hyp_in_fwd=0|1, dwh_in_bwd=0|1, dwh_split=<n>, fwd_pair=0|1,
 //            bwd_lean=0|1, pair_hyp_epi, mix_generic, lambda_path=1 (the TD(lambda) passes of the mixer tail even at
-//            mq_config.td_lambda = 0); COMA's where they are used (coma_host.hpp): coma_chain=0 (mc_create),
-//            coma_overlap=0 (per train())
+//            mq_config.td_lambda = 0), ffn_dp2_blocks=<n> (feed-forward agent: ffn_dp2_kernel's workgroup cap);
+//            COMA's where they are used (coma_host.hpp): coma_chain=0 (mc_create), coma_overlap=0 (per train())
 //   MQ_DIAG  diagnostics and test hooks, read per train(): pair_stamp=<file> (the row-pair forward's s_memtime
 //            stamps), bwd_stamp=<file> (the fused BPTT's), hyp_sched=<hex> (the pair forward's in-loop hypernet tile
 //            schedule), coma_trace (the COMA chain's phase times), coma_fault=<workgroup> (a chain workgroup that

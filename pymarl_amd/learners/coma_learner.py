@@ -37,6 +37,7 @@ import torch as th
 from torch.optim import RMSprop
 
 from .. import _lib
+from ..modules.agents.rnn_agent import use_rnn_config
 from ..modules.critics.coma import COMACritic
 from ..modules.flat import pack, rebind
 from .dp import DPCheck, SharedComm, dp_world, local_shard, native_comm_wanted, shard_bounds
@@ -76,6 +77,10 @@ class COMALearner:
         if getattr(args, "optimizer", None) not in (None, "rmsprop"):
             # the critic chain steps RMSprop in registers (include/mc_coma.h): never train on silently with another
             raise ValueError("COMALearner supports optimizer: rmsprop only (got {}).".format(args.optimizer))
+        if not use_rnn_config(args):
+            # the actor's BPTT is the GRU's (include/mc_coma.h): never train a GRU where the config asked for none
+            raise ValueError("COMALearner does not support use_rnn: False (the feed-forward agent): its actor is the "
+                             "GRU agent.")
         self.n_agents = args.n_agents
         self.n_actions = args.n_actions
         self.mac = mac

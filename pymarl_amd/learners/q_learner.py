@@ -16,6 +16,10 @@ the step's last launch); `standardise_rewards: True` standardises the rewards wi
 device (`self.rew_ms`, reward_norm_kernel, mq_set_reward_norm) before the target is formed. Without the keys nothing
 changes.
 
+Opt-in `use_rnn: False` (epymarl's key, modules/agents/rnn_agent.py): the agent's `rnn` is a Linear + ReLU, and the
+step runs the feed-forward agent's GEMM chain in the recurrence's place (ffn_kernels.hpp, mq_config.agent);
+`last_agent()` says which agent the last step ran. Without the key nothing changes.
+
 Data parallel: with `args.learner_dp = True` and torch.distributed initialised (RCCL, one process
 per GPU), every rank calls train() with the SAME GLOBAL sample, as run.py:207-219 does unchanged (ranks share the
 seed, so the sampled ids agree; ids and contents checked on a call-count schedule, `args.learner_dp_check`); the
@@ -40,6 +44,7 @@ from torch.optim import Adam, RMSprop
 
 from .. import _lib
 from ..components.episode_buffer import PrioritizedBatch, is_replay_view
+from ..modules.agents.rnn_agent import agent_kind, hidden_dim
 from ..modules.flat import pack, rebind
 from .dp import DPCheck, SharedComm, allreduce_grad_buffer, dp_world, local_shard, native_comm_wanted
 from ..modules.mixers.qmix import QMixer, hypernet_config
@@ -62,7 +67,9 @@ def make_config(args, mixer, input_dim=None, max_batch=1, max_seq=2):
     cfg.obs_dim = int(obs)
     st = getattr(args, "state_shape", 1)
     cfg.state_dim = int(st if isinstance(st, int) else th.Size(st).numel())
-    cfg.rnn_hidden_dim = args.rnn_hidden_dim
+    cfg.rnn_hidden_dim = hidden_dim(args)   # epymarl's hidden_dim when rnn_hidden_dim is absent
+    # epymarl's use_rnn: False selects the feed-forward agent (rnn = Linear + ReLU); absent or True: the GRU
+    cfg.agent = agent_kind(args)
     cfg.mixing_embed_dim = getattr(args, "mixing_embed_dim", 32)
     cfg.mixer = mixer
     cfg.double_q = int(bool(getattr(args, "double_q", True)))
@@ -566,6 +573,12 @@ class QLearner:
         d["dwh"] = ("red1", "bptt_grid")[d["dwh"]]
         return d
 
+    def last_agent(self):
+        """mq_last_agent of the last train(): 0 when the GRU agent ran; otherwise a bit set, bit 0 = the feed-forward
+        agent (use_rnn: False) ran, bits 1 / 2 = its forward / backward was a fused kernel (never set: the step runs
+        the GEMM chain)."""
+        return int(self._handle.lib.mq_last_agent(self._handle.h))
+
     def last_cur_max_actions(self):
         """Double-Q greedy actions of the last step as (B, T, n) int64 (q_learner.py:75)."""
         B, Tp = self._last_batch
@@ -581,7 +594,9 @@ class QLearner:
         unweighted |td * mask| the priority write-back summed, as (B, T, 1) (no mixer: summed over the agents).
         After a step of the two-layer hypernet (last_plan()["hyper_layers"] == 2): 7: the online net's layer-1
         pre-activations [hyper_w_1.0 | hyper_w_final.0] as (B, T, 2 * hypernet_embed). After a step that standardised
-        its rewards (last_plan()["reward_norm"] == 1): 8: the standardised rewards the step read, as (B, T, 1)."""
+        its rewards (last_plan()["reward_norm"] == 1): 8: the standardised rewards the step read, as (B, T, 1). After
+        a step of the feed-forward agent (last_agent() & 1): 9: the online net's h = relu(rnn(x1)) as
+        (B, T+1, n, 64)."""
         B, Tp = self._last_batch
         n, A = self.args.n_agents, self.args.n_actions
         cnt = ctypes.c_int64()
@@ -591,7 +606,7 @@ class QLearner:
         _lib.check(h.lib.mq_copy_intermediate(h.h, which, _lib.ptr(out), ctypes.byref(cnt), _lib.stream_ptr()))
         if which in (0, 1):
             return out.view(Tp, B, n, A).permute(1, 0, 2, 3)
-        if which == 3:
+        if which in (3, 9):
             return out.view(Tp, B, n, -1).permute(1, 0, 2, 3)
         if which in (4, 5, 6, 7, 8):
             return out.view(Tp - 1, B, -1).permute(1, 0, 2)

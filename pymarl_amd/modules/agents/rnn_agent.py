@@ -2,9 +2,15 @@
 
 Same submodules and parameter names (fc1, rnn, fc2), so state_dicts interchange with the reference. `forward`
 runs the HIP `mq_agent_forward` kernel; inside the learner the whole unroll is fused into the train step.
+
+Opt-in `use_rnn: False` (epymarl's key): `rnn` is then `nn.Linear(64, 64)` followed by a ReLU instead of the GRUCell,
+    x1 = relu(fc1(inputs));  h = relu(rnn(x1));  q = fc2(h)
+with the incoming hidden state ignored and `h` returned in its place; the state_dict is epymarl's (fc1.weight,
+fc1.bias, rnn.weight, rnn.bias, fc2.weight, fc2.bias). Without the key, or with True, nothing changes.
 """
 from collections import OrderedDict
 
+import numpy as np
 import torch as th
 import torch.nn as nn
 
@@ -21,20 +27,51 @@ def input_dim(input_shape):
     return int(input_shape)
 
 
+def use_rnn_config(args):
+    """epymarl's use_rnn: True (or the key absent / None) is the GRU agent, False the feed-forward one. Not a bool:
+    ValueError."""
+    v = getattr(args, "use_rnn", True)
+    if v is None:
+        return True
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError("use_rnn must be True or False, got {!r}.".format(v))
+    return bool(v)
+
+
+def hidden_dim(args):
+    """The agent's hidden width: rnn_hidden_dim, or epymarl's hidden_dim when rnn_hidden_dim is absent."""
+    v = getattr(args, "rnn_hidden_dim", None)
+    if v is None:
+        v = getattr(args, "hidden_dim", None)
+    if v is None:
+        raise AttributeError("args has neither rnn_hidden_dim nor hidden_dim")
+    return int(v)
+
+
+def agent_kind(args):
+    """MQ_AGENT_* of the args (mq_config.agent)."""
+    return _lib.AGENT_GRU if use_rnn_config(args) else _lib.AGENT_FFN
+
+
 class RNNAgent(FlatModule):
     def __init__(self, input_shape, args):
         super().__init__()
         self.args = args
         self.input_shape = input_shape
         self.input_dim = input_dim(input_shape)
-        self.fc1 = nn.Linear(self.input_dim, args.rnn_hidden_dim)
-        self.rnn = nn.GRUCell(args.rnn_hidden_dim, args.rnn_hidden_dim)
-        self.fc2 = nn.Linear(args.rnn_hidden_dim, args.n_actions)
+        self.use_rnn = use_rnn_config(args)
+        self.hidden_dim = hidden_dim(args)
+        self.fc1 = nn.Linear(self.input_dim, self.hidden_dim)
+        if self.use_rnn:
+            self.rnn = nn.GRUCell(self.hidden_dim, self.hidden_dim)
+        else:
+            self.rnn = nn.Linear(self.hidden_dim, self.hidden_dim)
+        self.fc2 = nn.Linear(self.hidden_dim, args.n_actions)
         self._init_flat()
         self._handle = None
 
     def init_hidden(self):
-        return self.fc1.weight.new_zeros(1, self.args.rnn_hidden_dim)
+        return self.fc1.weight.new_zeros(1, self.hidden_dim)
 
     def handle(self):
         """Inference handle (agent-only layout) bound to this module's flat parameters."""
@@ -46,15 +83,19 @@ class RNNAgent(FlatModule):
             self._handle = (h, self._flat.data_ptr())
         return self._handle[0]
 
-    def forward(self, inputs, hidden_state):
+    def forward(self, inputs, hidden_state=None):
         if isinstance(inputs, (dict, OrderedDict)):
             inputs = inputs["1d"]
         _lib.require_gpu(inputs)
         x = inputs.reshape(-1, self.input_dim).float().contiguous()
-        h_in = hidden_state.reshape(-1, self.args.rnn_hidden_dim).float().contiguous()
-        h_out = th.empty_like(h_in)
         q = th.empty(x.shape[0], self.args.n_actions, dtype=th.float32, device=x.device)
         hd = self.handle()
+        if self.use_rnn:
+            h_in = hidden_state.reshape(-1, self.hidden_dim).float().contiguous()
+            h_out = th.empty_like(h_in)
+        else:   # any hidden_state: it is not read
+            h_in = None
+            h_out = th.empty(x.shape[0], self.hidden_dim, dtype=th.float32, device=x.device)
         _lib.check(hd.lib.mq_agent_forward(hd.h, _lib.ptr(x), x.shape[0], _lib.ptr(h_in), _lib.ptr(h_out),
                                            _lib.ptr(q), 0, _lib.stream_ptr()))
         return q, h_out

@@ -1,0 +1,352 @@
+"""The feed-forward agent (use_rnn: False, epymarl's key) without a GPU: the key's parsing and its errors, the module's
+state_dict against epymarl's restated module (tests/ffn_ref.RefFFAgent), the COMA refusal, the plan through
+tests/host/ffn_plan_probe.cpp, and the conditions the GPU gradient gate of tests/test_gpu_ffn.py rests on (the float64
+reference is finite on every row and its seeds keep clear of the mixer's kinks; the float32 run leaves the gate room)."""
+import ctypes
+import json
+import os
+import shutil
+import subprocess
+from types import SimpleNamespace as SN
+
+import numpy as np
+import pytest
+import torch as th
+
+from pymarl_amd import _lib
+from pymarl_amd.learners.q_learner import make_config
+from pymarl_amd.modules.agents.rnn_agent import RNNAgent, agent_kind, hidden_dim, use_rnn_config
+from pymarl_amd.utils.synthetic import agent_param_shapes
+from tests import ffn_ref as R
+from tests import ref64
+from tests.test_plan_host import CUS, HIPCC, MIXERS, PARENT, probe  # noqa: F401  (probe: plan_probe.cpp's fixture)
+from tests.test_gpu_grad_blocks import ROWS as GRU_ROWS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def agent_args(**kw):
+    base = dict(rnn_hidden_dim=64, n_actions=9, n_agents=3, obs_shape=30, state_shape=48, obs_last_action=True,
+                obs_agent_id=True)
+    base.update(kw)
+    return SN(**{k: v for k, v in base.items() if v is not Ellipsis})
+
+
+# ---------------------------------------------------------------------------------------------- the key
+def test_use_rnn_parsing():
+    assert use_rnn_config(agent_args()) is True   # absent
+    assert use_rnn_config(agent_args(use_rnn=None)) is True
+    assert use_rnn_config(agent_args(use_rnn=True)) is True
+    assert use_rnn_config(agent_args(use_rnn=False)) is False
+    assert use_rnn_config(agent_args(use_rnn=np.bool_(False))) is False
+    for bad in (0, 1, "False", "false", 0.0, [False]):
+        with pytest.raises(ValueError, match="use_rnn"):
+            use_rnn_config(agent_args(use_rnn=bad))
+        with pytest.raises(ValueError, match="use_rnn"):
+            RNNAgent(42, agent_args(use_rnn=bad))
+    assert agent_kind(agent_args()) == _lib.AGENT_GRU == 0
+    assert agent_kind(agent_args(use_rnn=False)) == _lib.AGENT_FFN == 1
+
+
+def test_hidden_dim_alias():
+    assert hidden_dim(agent_args()) == 64
+    assert hidden_dim(agent_args(rnn_hidden_dim=..., hidden_dim=64)) == 64
+    assert hidden_dim(agent_args(rnn_hidden_dim=64, hidden_dim=128)) == 64   # rnn_hidden_dim wins when present
+    with pytest.raises(AttributeError):
+        hidden_dim(agent_args(rnn_hidden_dim=...))
+    a = RNNAgent(42, agent_args(rnn_hidden_dim=..., hidden_dim=64, use_rnn=False))
+    assert a.rnn.weight.shape == (64, 64) and a.init_hidden().shape == (1, 64)
+    cfg = make_config(agent_args(rnn_hidden_dim=..., hidden_dim=64, use_rnn=False), _lib.MIXER_VDN)
+    assert (cfg.rnn_hidden_dim, cfg.agent) == (64, 1)
+
+
+def test_make_config_sets_the_agent_kind():
+    assert make_config(agent_args(), _lib.MIXER_QMIX).agent == 0
+    assert make_config(agent_args(use_rnn=True), _lib.MIXER_QMIX).agent == 0
+    assert make_config(agent_args(use_rnn=False), _lib.MIXER_QMIX).agent == 1
+    with pytest.raises(ValueError, match="use_rnn"):
+        make_config(agent_args(use_rnn="no"), _lib.MIXER_QMIX)
+
+
+@pytest.mark.parametrize("agent,hidden,word", [(2, 64, b"agent"), (-1, 64, b"agent"), (1, 32, b"rnn_hidden_dim"),
+                                               (1, 128, b"rnn_hidden_dim")])
+def test_library_rejects_bad_values_before_any_hip_call(agent, hidden, word):
+    lib = _lib.load()
+    cfg = _lib.MQConfig(n_agents=3, n_actions=9, obs_dim=30, state_dim=48, rnn_hidden_dim=hidden, mixing_embed_dim=32,
+                        mixer=2, max_batch=4, max_seq=11, agent=agent)
+    h = ctypes.c_void_p()
+    assert lib.mq_create(ctypes.byref(cfg), ctypes.byref(h)) == 1   # MQ_ERR_ARG
+    assert word in lib.mq_last_error()
+    assert lib.mq_last_agent(None) == -1
+
+
+def test_config_struct_ends_with_the_agent_field():
+    assert _lib.MQConfig._fields_[-1][0] == "agent"
+    assert _lib.MQConfig.agent.offset == ctypes.sizeof(_lib.MQConfig) - 4
+    assert _lib.MQConfig().agent == 0   # a zeroed struct is the GRU
+    assert _lib.PARAM_NAMES[-2:] == ["rnn.weight", "rnn.bias"] and _lib.P_COUNT == 24
+
+
+# ---------------------------------------------------------------------------------------------- the module
+@pytest.mark.parametrize("I,A", [(42, 9), (7, 2), (155, 33)])
+def test_state_dict_is_epymarls(I, A):
+    th.manual_seed(I)
+    ref = R.RefFFAgent(I, A)
+    ours = RNNAgent(I, agent_args(n_actions=A, use_rnn=False))
+    shapes = R.ff_agent_shapes(I, A)
+    assert list(ours.state_dict()) == list(ref.state_dict()) == list(shapes)
+    assert [n for n, _ in ours.named_parameters()] == list(shapes)
+    for k, v in ref.state_dict().items():
+        assert tuple(ours.state_dict()[k].shape) == tuple(v.shape) == shapes[k], k
+    ours.load_state_dict(ref.state_dict())
+    for k, v in ref.state_dict().items():
+        assert th.equal(ours.state_dict()[k], v), k
+    flat = th.cat([p.detach().reshape(-1) for p in ref.parameters()])
+    assert th.equal(ours.flat_params(), flat)   # the flat buffer the kernels read holds them in that order
+
+
+def test_plain_torch_save_of_epymarls_state_dict_loads(tmp_path):
+    th.manual_seed(3)
+    ref = R.RefFFAgent(42, 9)
+    th.save(ref.state_dict(), str(tmp_path / "agent.th"))
+    ours = RNNAgent(42, agent_args(use_rnn=False))
+    ours.load_state_dict(th.load(str(tmp_path / "agent.th"), weights_only=True))
+    for k, v in ref.state_dict().items():
+        assert th.equal(ours.state_dict()[k], v), k
+    gru = RNNAgent(42, agent_args())   # and a GRU module refuses it, as before
+    with pytest.raises(RuntimeError, match="rnn.weight"):
+        gru.load_state_dict(th.load(str(tmp_path / "agent.th"), weights_only=True))
+    th.save(ours.state_dict(), str(tmp_path / "ours.th"))   # we write, epymarl loads
+    back = R.RefFFAgent(42, 9)
+    back.load_state_dict(th.load(str(tmp_path / "ours.th"), weights_only=True))
+
+
+@pytest.mark.parametrize("kw", [{}, dict(use_rnn=True), dict(use_rnn=None)])
+def test_without_the_key_the_module_is_todays(kw):
+    a = RNNAgent(42, agent_args(**kw))
+    shapes = agent_param_shapes(42, 64, 9)
+    assert isinstance(a.rnn, th.nn.GRUCell) and a.use_rnn
+    assert list(a.state_dict()) == list(shapes)
+    for k, v in a.state_dict().items():
+        assert tuple(v.shape) == shapes[k], k
+
+
+def test_restated_module_agrees_with_ref_steps_unroll():
+    th.manual_seed(4)
+    m = R.RefFFAgent(9, 4).double()
+    obs = th.randn(2, 3, 1, 9, dtype=th.float64)
+    q, pre, pre2 = R._unroll(dict(m.state_dict()), obs, th.zeros(2, 3, 1, 4, dtype=th.float64), (False, False),
+                             th.float64)
+    qm, hm = m(obs.reshape(-1, 9), th.full((6, 64), float("nan"), dtype=th.float64))   # the hidden state is ignored
+    assert th.allclose(q.reshape(-1, 4), qm, rtol=1e-13, atol=1e-13)
+    assert th.allclose(th.relu(pre2).reshape(-1, 64), hm, rtol=1e-13, atol=1e-13)
+
+
+# ---------------------------------------------------------------------------------------------- COMA
+def test_coma_refuses_the_key():
+    from pymarl_amd.controllers import REGISTRY as mac_REGISTRY
+    from pymarl_amd.learners import REGISTRY as le_REGISTRY
+    from tests.gpu_helpers import make_coma_args, make_scheme
+    case = SN(n=3, A=9, O=30, S=48, B=2, target_update_interval=200, mask_before_softmax=True)
+    args = make_coma_args(case, use_rnn=False)
+    scheme = dict(make_scheme(case), actions_onehot={"vshape": (case.A,), "group": "agents"})
+    with pytest.raises(ValueError, match="use_rnn"):
+        mac_REGISTRY["basic_mac"](scheme, {"agents": case.n}, args)   # agent_output_type pi_logits: mc_policy's MAC
+    with pytest.raises(ValueError, match="use_rnn"):
+        le_REGISTRY["coma_learner"](None, scheme, None, args)
+    with pytest.raises(ValueError, match="use_rnn"):
+        le_REGISTRY["coma_learner"](None, scheme, None, make_coma_args(case, use_rnn="yes"))
+    mac = mac_REGISTRY["basic_mac"](scheme, {"agents": case.n}, make_coma_args(case))   # without the key: as before
+    assert isinstance(mac.agent.rnn, th.nn.GRUCell)
+
+
+# ---------------------------------------------------------------------------------------------- the plan
+@pytest.fixture(scope="module")
+def fprobe(tmp_path_factory):
+    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
+        pytest.skip("no hipcc to build tests/host/ffn_plan_probe.cpp with")
+    exe = str(tmp_path_factory.mktemp("ffn_plan_probe") / "ffn_plan_probe")
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-O1",
+                    os.path.join(ROOT, "tests", "host", "ffn_plan_probe.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def run_probe(exe, argv, plan_env=""):
+    env = {k: v for k, v in os.environ.items() if k not in ("MQ_PLAN", "MQ_DIAG")}
+    if plan_env:
+        env["MQ_PLAN"] = plan_env
+    return subprocess.run([exe] + [str(a) for a in argv], env=env, check=True, capture_output=True, text=True).stdout
+
+
+def ffn_plan(fprobe, mixer, d, agent=1, layers=1, num_cu=CUS, plan_env=""):
+    argv = [num_cu, MIXERS[mixer], d["n"], d["A"], d["O"], d["S"], 32, 1, 1, 1, d["B"], d["T"] + 1, agent, layers]
+    return json.loads(run_probe(fprobe, argv, plan_env))
+
+
+ZERO_ITEMS = ("fused_fwd", "rw_fwd", "fused_bwd", "rw_bwd", "tiles", "bwd_lean", "dwh")
+
+
+@pytest.mark.parametrize("row", list(R.ROW_SHAPES))
+def test_ffn_plan_of_every_row(fprobe, row):
+    spec = R.ROW_SHAPES[row]
+    d = spec["dims"]
+    layers = 2 if spec.get("He") else 1
+    p = ffn_plan(fprobe, "qmix", d, layers=layers)
+    RT = (d["T"] + 1) * d["B"] * d["n"]
+    assert (p["agent"], p["ffn"], p["rows"]) == (1, 1, d["B"] * d["n"]), p
+    assert p["hyp_own_launch"] == 1 and p["dwh_in_bwd"] == 0, p   # the hypernet is a launch of its own
+    assert p["dwh_in_red1"] == (1 if layers == 1 else 0), p       # dW_hyper rides with reduction pass 1
+    assert p["hyper_layers"] == layers and 1 <= p["nsplit_mix"] <= 16, p
+    for k in ZERO_ITEMS:
+        assert p[k] == 0, (k, p)
+    # every workgroup of ffn_dp2_kernel owns a multiple of four rows, and together they cover the RT rows exactly once
+    assert p["ffn_rpb"] % 4 == 0 and p["ffn_nblk2"] <= 1024
+    assert (p["ffn_nblk2"] - 1) * p["ffn_rpb"] < RT <= p["ffn_nblk2"] * p["ffn_rpb"], p
+    for ns in (p["dw1_ns"], p["ffn_wr_ns"]):   # every split-K slice is non-empty under the 16-row rounding
+        chunk = (-(-RT // ns) + 15) // 16 * 16
+        assert 1 <= ns <= 128 and (ns - 1) * chunk < RT, (ns, RT)
+    for mixer, hyper in (("vdn", 0), ("none", 0)):
+        q = ffn_plan(fprobe, mixer, d)
+        assert (q["hyper"], q["hyp_own_launch"], q["dwh_in_red1"], q["hyper_layers"]) == (hyper, 0, 0, 0), q
+    want_mix = {"A33": ("generic", "stream"), "n17": ("stream",)}.get(row, ("fast16",))
+    assert _lib.MIX_NAMES[p["mix"]] in want_mix, p
+    if row == "split":   # two split-K slices of both weight-gradient GEMMs, the second shorter
+        assert p["ffn_wr_ns"] == 2 and p["dw1_ns"] == 2 and RT % 2 == 0 and (RT // 2) % 16 == 0, p
+    if row == "walk":   # more than one round of four rows per ffn_dp2_kernel workgroup, and many slices
+        assert p["ffn_rpb"] == 8 and p["ffn_nblk2"] == 528 and p["ffn_wr_ns"] == 16 and p["dw1_ns"] == 16, p
+    if row == "tiles":   # MQ_PLAN ffn_dp2_blocks caps the workgroups: two, of 19 rounds, the second partial (71 rows)
+        q = ffn_plan(fprobe, "qmix", d, plan_env="ffn_dp2_blocks=2")
+        assert (q["ffn_nblk2"], q["ffn_rpb"]) == (2, 76) and RT == 147, q
+        assert {k: v for k, v in q.items() if not k.startswith("ffn_")} == \
+            {k: v for k, v in p.items() if not k.startswith("ffn_")}
+        assert ffn_plan(fprobe, "qmix", d, plan_env="ffn_dp2_blocks=5000")["ffn_nblk2"] == p["ffn_nblk2"]
+    if row == "A33":   # the switch still reaches the mixer tail
+        assert _lib.MIX_NAMES[ffn_plan(fprobe, "qmix", d, plan_env="mix_generic")["mix"]] == "generic"
+
+
+def test_ffn_plan_ignores_the_recurrences_switches_and_the_cu_count(fprobe):
+    d = dict(R.ROW_SHAPES["part"]["dims"], B=100)   # R = 300 rows: past the CU count, where the GRU appends dW_hyper
+    base = ffn_plan(fprobe, "qmix", d)
+    for env in ("unfused_fwd", "row_tiles=1", "dwh_in_bwd=1", "hyp_in_fwd=1", "fwd_pair=1", "bwd_lean=0"):
+        assert ffn_plan(fprobe, "qmix", d, plan_env=env) == base, env
+    assert ffn_plan(fprobe, "qmix", d, num_cu=0) == base
+    assert ffn_plan(fprobe, "qmix", d, plan_env="lambda_path=1")["td_lambda"] == 1
+    gru = ffn_plan(fprobe, "qmix", d, agent=0)
+    assert gru["dwh"] == 1 and base["dwh"] == 0
+
+
+@pytest.mark.parametrize("row", list(GRU_ROWS))
+def test_gru_kind_gets_plan_probes_answer_byte_for_byte(probe, fprobe, row):  # noqa: F811
+    from tests.gpu_helpers import switch_value
+    shape, mixer, switches, _ = GRU_ROWS[row]
+    rec = PARENT["rows"][row]
+    s = ref64.SHAPES[shape]
+    env = {}
+    for key, v in switches.items():
+        var, val = switch_value(env, key, v)
+        env[var] = val
+    assert set(env) <= {"MQ_PLAN"}
+    argv = [CUS, MIXERS[mixer], s["n"], s["A"], s["O"], s["S"], 32, 1, 1, 1, s["B"], rec["t_len"]]
+    old = run_probe(probe, argv, env.get("MQ_PLAN", ""))
+    new = run_probe(fprobe, argv + [0], env.get("MQ_PLAN", ""))
+    assert new == old, (row, new, old)
+
+
+# ---------------------------------------------------------------------------------------------- the gate's conditions
+MIXERS_OF = {"part": ("qmix", "vdn", "none"), "walk": ("vdn",)}
+
+
+@pytest.fixture(scope="module")
+def steps():
+    """{(row, mixer): [(case, params, targets, batch, float64 result)] for step 0 and step 1}, step 1 from the float64
+    reference's own RMSprop update of step 0."""
+    out = {}
+    for row in R.ROW_SHAPES:
+        for mixer in MIXERS_OF.get(row, ("qmix",)):
+            case = R.synth_case(row, mixer)
+            p = t = R.flat_of(case)
+            sq = np.zeros_like(p, np.float64)
+            recs = []
+            for k in range(2):
+                nb, _ = case.batch(k)
+                r = R.ref_step(case, p, t, nb)
+                recs.append((case, p, t, nb, r))
+                p, sq = R.rmsprop(case, p, sq, r.clipped_flat)
+                p = p.astype(np.float32)
+            out[row, mixer] = recs
+    return out
+
+
+@pytest.mark.parametrize("row", list(R.ROW_SHAPES))
+def test_reference_is_finite_and_clear_of_the_kinks(steps, row):
+    for mixer in MIXERS_OF.get(row, ("qmix",)):
+        for k, (case, p, t, nb, r) in enumerate(steps[row, mixer]):
+            assert np.isfinite(r.loss) and np.isfinite(r.clipped_flat).all() and r.norm > 0, (row, mixer, k)
+            assert (r.mask > 0).any()
+            if mixer == "qmix":
+                ref64.assert_clear_of_kinks(r, "{} step {}".format(row, k))
+            for name, g in r.grads.items():   # every tensor takes part
+                assert np.abs(g).max() > 0, (row, mixer, k, name)
+
+
+@pytest.mark.parametrize("flags", R.FLAGS)
+def test_flag_rows_are_finite_and_clear_of_the_kinks(flags):
+    case = R.synth_case("part", flags=flags)
+    assert case.I == 30 + (9 if flags[0] else 0) + (3 if flags[1] else 0)
+    p = R.flat_of(case)
+    nb, _ = case.batch(0)
+    r = R.ref_step(case, p, p, nb)
+    assert np.isfinite(r.clipped_flat).all()
+    ref64.assert_clear_of_kinks(r, "part flags {}".format(flags))
+    assert set(R.grad_blocks(case)) >= {"fc1.weight[obs]"}
+    assert ("fc1.weight[last_action]" in R.grad_blocks(case)) == flags[0]
+    assert ("fc1.weight[agent_id]" in R.grad_blocks(case)) == flags[1]
+
+
+def test_ragged_row_has_padded_steps_and_unfilled_previous_slots(steps):
+    for case, p, t, nb, r in steps["ragged", "qmix"]:
+        filled = nb["filled"][:, :, 0]
+        # a padded transition inside max_t: its loss term is masked, and the step behind it (slot t + 1, which the
+        # forward still runs) builds its last-action columns from an unfilled slot: zeros, whatever the storage holds
+        assert (filled[:, :-1] == 0).any() and (r.mask == 0).any()
+        assert filled.shape[1] == int(filled.sum(1).max())
+    for case, p, t, nb, r in steps["part", "qmix"]:   # and the other rows are full length
+        assert (nb["filled"] == 1).all()
+
+
+def test_float32_reference_leaves_the_gate_room(steps):
+    """e32 of every block on `part` is below TOL_CAP / TOL_ROOM: the cap never decides a block there."""
+    case, p, t, nb, r64 = steps["part", "qmix"][0]
+    r32 = R.ref_step(case, p, t, nb, dtype=th.float32, cur_max_override=r64.cur_max_actions,
+                     relu_override=r64.pre > 0, hid_relu_override=r64.pre2 > 0)
+    e32 = R.block_errors(r32.clipped_flat, r64.clipped, case)
+    assert set(R.ff_agent_shapes(case.I, case.A)) <= set(e32)
+    worst = max(e32, key=e32.get)
+    print("worst e32 {:.3g} at {}".format(e32[worst], worst))
+    assert e32[worst] < ref64.TOL_CAP / ref64.TOL_ROOM, (worst, e32[worst])
+    assert abs(r32.norm - r64.norm) <= 1e-5 * r64.norm
+
+
+def test_overrides_at_the_references_own_decisions_change_nothing(steps):
+    case, p, t, nb, r = steps["tiles", "qmix"][0]
+    r2 = R.ref_step(case, p, t, nb, cur_max_override=r.cur_max_actions, relu_override=r.pre > 0,
+                    hid_relu_override=r.pre2 > 0)
+    assert np.array_equal(r2.clipped_flat, r.clipped_flat)
+    c = R.classify(r, r.cur_max_actions, r.pre > 0, r.pre2 > 0)
+    assert c["dq_flips"] == c["relu_flips"] == c["hid_relu_flips"] == 0
+    assert c["hid_relu_decisions"] == r.pre2.size
+    flipped = r.pre2 > 0
+    flipped[0, 0, 0, 0] = not flipped[0, 0, 0, 0]   # and a flipped decision is counted
+    assert R.classify(r, r.cur_max_actions, r.pre > 0, flipped)["hid_relu_flips"] == 1
+
+
+def test_ffn_reference_differs_from_the_gru_reference(steps):
+    """The same shape and data under the GRU reference give another loss: a learner that ignored the key cannot pass."""
+    case, p, t, nb, r = steps["part", "qmix"][0]
+    from tests.golden_utils import SynthCase
+    d = R.ROW_SHAPES["part"]["dims"]
+    gcase = SynthCase("gru_part", n_episodes=d["B"], steps=2, mixer="qmix", ragged=False, min_len=1, **d)
+    gp = np.concatenate([v.ravel() for v in list(gcase.agent_params.values()) + list(gcase.mixer_params.values())])
+    rg = ref64.ref64_step(gcase, gp, gp, gcase.batch(0)[0])
+    assert abs(rg.loss - r.loss) > 1e-3 * abs(r.loss)
+    assert gp.size != p.size
