@@ -1,8 +1,13 @@
-// Host side of the COMA learner step (include/mc_coma.h), included at the end of mq_learner.hip so it shares the
-// QMIX learner's error handling, replay plumbing and agent kernels. The agent (RNNAgent) forward / BPTT reuses an
-// internal mq_handle (no mixer) for its workspace; the critic has its own.
+// Host side of the COMA learner step (include/mc_coma.h). It shares the QMIX learner's error handling
+// (host_util.hpp), replay plumbing (learner_handle.hpp) and agent kernels. The agent (RNNAgent) forward / BPTT reuses
+// an internal mq_handle (no mixer) for its workspace; the critic has its own.
+#pragma once
 #include "../../include/mc_coma.h"
 #include "coma_chain.hpp"
+#include "gru_fwd_fused.hpp"
+#include "gru_kernels.hpp"
+#include "learner_handle.hpp"
+#include "reduce_plan.hpp"
 
 struct mc_handle {
   mc_config cfg;
@@ -13,7 +18,7 @@ struct mc_handle {
   int64_t Pa, Pc;
   float *agent = nullptr, *agrad = nullptr, *asq = nullptr, *critic = nullptr, *tcritic = nullptr,
         *cgrad = nullptr, *csq = nullptr, *stats = nullptr;
-  void* ws = nullptr;
+  DevBuf<float> ws;   // one allocation, carved by mc_create's table
   // critic workspace
   float *X, *H1t, *H2t, *Qt, *tgt, *msum, *H1p, *H1c, *H2c, *dH1c, *dH2c, *dqc, *qvals, *cpart, *cnorm, *crec;
   float *Pshadow, *SQshadow;
@@ -29,7 +34,7 @@ struct mc_handle {
   int num_cu = 0;
   bool chain_attr = false;
   int last_path = -1;
-  unsigned long long* chain_trace = nullptr;   // MQ_DIAG coma_trace: phase timestamps printed after each train
+  DevBuf<unsigned long long> chain_trace;   // MQ_DIAG coma_trace: phase timestamps printed after each train
   // data parallel (mc_set_data_parallel)
   mc_allreduce_fn dp_fn = nullptr;
   void* dp_ctx = nullptr;
@@ -38,12 +43,19 @@ struct mc_handle {
   int64_t dp_scratch_n = 0;
   std::vector<float> dp_msum;
   ncclComm_t comm = nullptr;   // mc_comm_attach: native RCCL exchange steps
-  float* comm_scratch = nullptr;
+  DevBuf<float> comm_scratch;   // [8 * max_seq], allocated by the first mc_comm_attach / mc_comm_use
   bool comm_owned = false;   // mc_comm_attach created it; mc_comm_use borrows the caller's
   // mc_set_actor_shard: replicated-critic data parallelism (every rank runs the critic on the whole batch, the actor
   // on episodes [shard_lo, shard_hi) with one all-reduce of the agent gradient); off while shard_hi <= shard_lo
   int shard_lo = 0, shard_hi = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+
+  ~mc_handle() {   // the buffers free themselves
+    if (comm && comm_owned) (void)ncclCommDestroy(comm);
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    mq_destroy(ah);
+  }
 };
 
 namespace {
@@ -160,7 +172,7 @@ int mc_create(const mc_config* cfg, mc_handle** out) {
   mq_handle* ah = nullptr;
   int rc = mq_create(&ac, &ah);
   if (rc) return rc;
-  mc_handle* h = new mc_handle();
+  std::unique_ptr<mc_handle> h(new mc_handle());   // owns ah from here: a failure below frees both
   h->cfg = c;
   h->ah = ah;
   h->I = ah->I;
@@ -182,64 +194,40 @@ int mc_create(const mc_config* cfg, mc_handle** out) {
   const int64_t ns2 = kNsplitMax;
   const int64_t red_tmp = kRedZ * ((int64_t)mq::H * h->I + mq::H) + kRedZ * h->ah->len_rnn +
                           kRedZ * (A * mq::H + A) + kRedZ * 8;
-  int64_t sizes[] = {
-      Tp * R * h->Kp,              // X
-      Tp * R * CH, Tp * R * CH,    // H1t, H2t
-      Tp * R * A,                  // Qt
-      T * R, T,                    // tgt, msum
-      (int64_t)std::max(l1_slices(h->Kp), cc_nk(h->Kc)) * R * CH,   // H1p (three-launch l1 or chain phase A)
-      R * CH, R * CH, R * CH, R * CH,   // H1c H2c dH1c dH2c
-      R, R,                        // dqc, actc
-      T * R * A,                   // qvals
-      nhead * 8, std::max<int64_t>(nwg, 1024), T * 8,   // cpart, cnorm (chain: 256 8-B granules + flags), crec
-      h->Pc, h->Pc,                // shadow params / square_avg (the chain's gradient exchange: Pshadow)
-      8,                           // cstate (+ the critic chain's sync words)
-      RTa * h->Ap, RTa * mq::H, RTa * A,   // dL, dHo, pi
-      ((RTa + 3) / 4) * 8,         // ppart
-      ns2 * (A * mq::H + A),       // slab_fc2
-      red_tmp,                     // red_tmp
-      4096,                        // norm_part
-      2 * h->Pc,                   // Pbak
+  const WsTable ws = {
+      {"X", Tp * R * h->Kp, &h->X},
+      {"H1t", Tp * R * CH, &h->H1t}, {"H2t", Tp * R * CH, &h->H2t},
+      {"Qt", Tp * R * A, &h->Qt},
+      {"tgt", T * R, &h->tgt}, {"msum", T, &h->msum},
+      // three-launch l1 or chain phase A
+      {"H1p", (int64_t)std::max(l1_slices(h->Kp), cc_nk(h->Kc)) * R * CH, &h->H1p},
+      {"H1c", R * CH, &h->H1c}, {"H2c", R * CH, &h->H2c}, {"dH1c", R * CH, &h->dH1c}, {"dH2c", R * CH, &h->dH2c},
+      {"dqc", R, &h->dqc}, {"actc", R, nullptr, &h->actc},
+      {"qvals", T * R * A, &h->qvals},
+      {"cpart", nhead * 8, &h->cpart},
+      {"cnorm", std::max<int64_t>(nwg, 1024), &h->cnorm},   // chain: 256 8-B granules + flags
+      {"crec", T * 8, &h->crec},
+      // shadow params / square_avg (the chain's gradient exchange: Pshadow)
+      {"Pshadow", h->Pc, &h->Pshadow}, {"SQshadow", h->Pc, &h->SQshadow},
+      {"cstate", 8, nullptr, &h->cstate},   // + the critic chain's sync words
+      {"dL", RTa * h->Ap, &h->dL}, {"dHo", RTa * mq::H, &h->dHo}, {"pi", RTa * A, &h->pi},
+      {"ppart", ((RTa + 3) / 4) * 8, &h->ppart},
+      {"slab_fc2", ns2 * (A * mq::H + A), &h->slab_fc2},
+      {"red_tmp", red_tmp, &h->red_tmp},
+      {"norm_part", 4096, &h->norm_part},
+      {"Pbak", 2 * h->Pc, &h->Pbak},
   };
-  const int NS = (int)(sizeof(sizes) / sizeof(sizes[0]));
-  int64_t total = 0, offs[32];
-  for (int i = 0; i < NS; ++i) { offs[i] = total; total += align_up(std::max<int64_t>(sizes[i], 1)); }
-  hipError_t e = hipMalloc(&h->ws, total * sizeof(float));
-  if (e != hipSuccess) {
-    mq_destroy(ah);
-    delete h;
-    return set_err(MQ_ERR_HIP, std::string("COMA workspace hipMalloc: ") + hipGetErrorString(e));
-  }
-  float* b = (float*)h->ws;
-  int k = 0;
-  h->X = b + offs[k++]; h->H1t = b + offs[k++]; h->H2t = b + offs[k++]; h->Qt = b + offs[k++];
-  h->tgt = b + offs[k++]; h->msum = b + offs[k++]; h->H1p = b + offs[k++];
-  h->H1c = b + offs[k++]; h->H2c = b + offs[k++]; h->dH1c = b + offs[k++]; h->dH2c = b + offs[k++];
-  h->dqc = b + offs[k++]; h->actc = (int*)(b + offs[k++]);
-  h->qvals = b + offs[k++]; h->cpart = b + offs[k++]; h->cnorm = b + offs[k++]; h->crec = b + offs[k++];
-  h->Pshadow = b + offs[k++]; h->SQshadow = b + offs[k++];
-  h->cstate = (int*)(b + offs[k++]);
-  h->dL = b + offs[k++]; h->dHo = b + offs[k++]; h->pi = b + offs[k++]; h->ppart = b + offs[k++];
-  h->slab_fc2 = b + offs[k++]; h->red_tmp = b + offs[k++]; h->norm_part = b + offs[k++];
-  h->Pbak = b + offs[k++];
+  if ((rc = ws_carve(h->ws, ws, "COMA workspace hipMalloc"))) return rc;
   h->chain_env = plan_int("coma_chain", 1) != 0;   // MQ_PLAN coma_chain=0: three launches per critic step
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&h->num_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     h->num_cu = 0;
-  *out = h;
+  *out = h.release();
   return MQ_OK;
 }
 
 int mc_destroy(mc_handle* h) {
-  if (!h) return MQ_OK;
-  if (h->ws) (void)hipFree(h->ws);
-  if (h->chain_trace) (void)hipFree(h->chain_trace);
-  if (h->comm && h->comm_owned) (void)ncclCommDestroy(h->comm);
-  if (h->comm_scratch) (void)hipFree(h->comm_scratch);
-  for (auto& e : h->ev)
-    if (e) (void)hipEventDestroy(e);
-  mq_destroy(h->ah);
   delete h;
   return MQ_OK;
 }
@@ -352,7 +340,7 @@ int mc_train_step(mc_handle* h, const mq_replay* batch, float epsilon, void* str
   av.t_len = T;
   const Rep rpa = repl ? make_rep(&av) : rp;
   const int qv_r0 = repl ? h->shard_lo * n : 0;   // this rank's first row in the critic's [T][B n][A] Q values
-  Dims d = make_dims(ah, &av);
+  Dims d = mq::make_dims(ah->cfg, av.batch_size, av.t_len, av.t_stride);
   const Lay L = make_lay(ah);
   Work w = ah->w;
   w.dHo = h->dHo;
@@ -399,8 +387,9 @@ int mc_train_step(mc_handle* h, const mq_replay* batch, float epsilon, void* str
     cc.crec = h->crec; cc.cstate = h->cstate; cc.sync = (unsigned*)(h->cstate + 2);   // zeroed above
     cc.NK = cc_nk(h->Kc); cc.NG = 8 * cc.NK; cc.NHEAD = (R + 15) / 16;
     cc.hp = ca.hp;
-    if (env_item("MQ_DIAG", "coma_trace") && !h->chain_trace)
-      MQ_HIP(hipMalloc(&h->chain_trace, 16 * 8 * sizeof(unsigned long long)));
+    if (env_item("MQ_DIAG", "coma_trace") &&
+        (rc = h->chain_trace.alloc(16 * 8, "hipMalloc(&h->chain_trace, 16 * 8 * sizeof(unsigned long long))")))
+      return rc;
     cc.trace = h->chain_trace;
     cc.fault_wg = env_int("MQ_DIAG", "coma_fault", -1);   // test hook: a workgroup that stops flagging
     // cnorm: [0, 2 G) the norm granules, [512, 512 + G) flagA, [768, 768 + NHEAD) flagB; no stale step tags
@@ -618,9 +607,9 @@ int mc_comm_attach(mc_handle* h, const uint8_t* id, int32_t rank, int32_t world)
   if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
   if (h->comm) return set_err(MQ_ERR_STATE, "a communicator is already attached");
   const int64_t n = 8LL * h->cfg.max_seq;
-  if (!h->comm_scratch) MQ_HIP(hipMalloc(&h->comm_scratch, n * sizeof(float)));
-  const int rc = comm_init(&h->comm, id, rank, world);
-  if (rc) return rc;
+  // (the allocation's name is the text its failure message has always carried)
+  int rc = h->comm_scratch.alloc(n, "hipMalloc(&h->comm_scratch, n * sizeof(float))");
+  if (rc || (rc = comm_init(&h->comm, id, rank, world))) return rc;
   h->comm_owned = true;
   return mc_set_data_parallel(h, mc_rccl_allreduce, h, rank, h->comm_scratch, n);
 }
@@ -632,7 +621,7 @@ int mc_comm_use(mc_handle* h, void* comm) {
   const ncclResult_t r = ncclCommUserRank((ncclComm_t)comm, &rank);
   if (r != ncclSuccess) return set_err(MQ_ERR_ARG, std::string("ncclCommUserRank: ") + ncclGetErrorString(r));
   const int64_t n = 8LL * h->cfg.max_seq;
-  if (!h->comm_scratch) MQ_HIP(hipMalloc(&h->comm_scratch, n * sizeof(float)));
+  if (const int rc = h->comm_scratch.alloc(n, "hipMalloc(&h->comm_scratch, n * sizeof(float))")) return rc;
   h->comm = (ncclComm_t)comm;
   h->comm_owned = false;
   return mc_set_data_parallel(h, mc_rccl_allreduce, h, rank, h->comm_scratch, n);

@@ -279,6 +279,9 @@ __global__ __launch_bounds__(256) void apply_adam_kernel(float* __restrict__ p, 
 // One BasicMAC.forward step for every (episode, agent) row: inputs [obs_t | onehot(a_{t-1}) | onehot(agent)],
 // fc1 -> relu -> GRUCell -> fc2. One 256-thread workgroup per row (rollout batches are small).
 // xin_dense != NULL: the inputs are given ([rows][I], RNNAgent.forward); otherwise they are built from the replay.
+// Dynamic LDS: xin [I rounded up to 4] | x1 [H] | h [H] | gi [3H] | gh [3H] | h1 [H].
+inline size_t mac_step_lds_bytes(int I) { return (size_t)(((I + 3) & ~3) + H * 3 + G3 * 2) * sizeof(float); }
+
 __global__ __launch_bounds__(256) void mac_step_kernel(Dims d, Rep rp, const float* __restrict__ P, Lay L, int t,
                                                        const float* __restrict__ xin_dense,
                                                        const float* __restrict__ h_in, float* __restrict__ h_out,
