@@ -42,6 +42,12 @@ EXPORTS = [
     "mc_comm_use", "mc_comm_detach",
 ]
 
+# Every symbol include/ma_a2c.h declares (the actor-critic learner; __graft_entry__.build() checks them too).
+MA_EXPORTS = [
+    "ma_create", "ma_destroy", "ma_param_offsets", "ma_bind", "ma_set_adam", "ma_set_reward_norm", "ma_train_step",
+    "ma_update_targets", "ma_critic_forward_workspace", "ma_critic_forward", "ma_copy_intermediate", "ma_last_plan",
+]
+
 # mc_allreduce_fn (include/mc_coma.h): int (*)(float* buf, int64_t count, void* stream, void* ctx)
 MC_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p)
 
@@ -87,6 +93,44 @@ class MCConfig(ctypes.Structure):
         ("optim_alpha", ctypes.c_float), ("optim_eps", ctypes.c_float), ("grad_norm_clip", ctypes.c_float),
         ("max_batch", ctypes.c_int32), ("max_seq", ctypes.c_int32),
     ]
+
+
+MA_CRITIC_CV, MA_CRITIC_AC = 0, 1   # MA_CRITIC_*
+MA_P_COUNT = 6
+MA_NTAIL = 8
+MA_NSTATS = 16
+MA_CRITIC_PARAMS = ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias"]
+# where ma_train_step leaves each logged stat in stats[MA_NSTATS] (include/ma_a2c.h)
+A2C_STATS = {"critic_loss": 0, "critic_grad_norm": 1, "td_error_abs": 2, "q_taken_mean": 3, "target_mean": 4,
+             "advantage_mean": 10, "pg_loss": 8, "agent_grad_norm": 9, "pi_max": 11}
+A2C_MASK_ELEMS = 5   # stats[5]: M = n_agents * sum(mask); 0 after a batch whose mask was empty
+
+
+class MAConfig(ctypes.Structure):
+    _fields_ = [
+        ("n_agents", ctypes.c_int32), ("n_actions", ctypes.c_int32), ("obs_dim", ctypes.c_int32),
+        ("state_dim", ctypes.c_int32), ("rnn_hidden_dim", ctypes.c_int32), ("critic_hidden", ctypes.c_int32),
+        ("critic_type", ctypes.c_int32), ("obs_last_action", ctypes.c_int32), ("obs_agent_id", ctypes.c_int32),
+        ("mask_before_softmax", ctypes.c_int32), ("q_nstep", ctypes.c_int32), ("add_value_last_step", ctypes.c_int32),
+        ("entropy_coef", ctypes.c_float), ("lr", ctypes.c_float), ("optim_alpha", ctypes.c_float),
+        ("optim_eps", ctypes.c_float), ("grad_norm_clip", ctypes.c_float), ("gamma_pow", ctypes.c_void_p),
+        ("max_batch", ctypes.c_int32), ("max_seq", ctypes.c_int32),
+    ]
+
+
+class MAAdam(ctypes.Structure):
+    """ma_adam: both optimisers' first-moment buffers (device pointers) and Adam's hyper-parameters."""
+    _fields_ = [("agent_exp_avg", ctypes.c_void_p), ("critic_exp_avg", ctypes.c_void_p), ("beta1", ctypes.c_float),
+                ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float)]
+
+
+class MAPlan(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in (
+        "rows", "rows_target", "k", "kp", "hidden", "vec16", "fwd_tiles", "vhead_blocks", "nstep_lds", "dv_blocks",
+        "ns_cw2", "ns_cw1", "policy_blocks", "policy_tail", "policy_lanes", "ap", "ns_aw1", "ns_aw2", "bwd_blocks", "reward_norm", "adam")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class MQPlan(ctypes.Structure):
@@ -196,6 +240,18 @@ def load(required=True):
         "mq_comm_free": ([vp], ctypes.c_int),
         "mc_comm_use": ([vp, vp], ctypes.c_int),
         "mc_comm_detach": ([vp], ctypes.c_int),
+        "ma_create": ([ctypes.POINTER(MAConfig), ctypes.POINTER(vp)], ctypes.c_int),
+        "ma_destroy": ([vp], ctypes.c_int),
+        "ma_param_offsets": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], ctypes.c_int),
+        "ma_bind": ([vp, vp, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
+        "ma_set_adam": ([vp, ctypes.POINTER(MAAdam)], ctypes.c_int),
+        "ma_set_reward_norm": ([vp, vp], ctypes.c_int),
+        "ma_train_step": ([vp, ctypes.POINTER(MQReplay), i64, vp], ctypes.c_int),
+        "ma_update_targets": ([vp, ctypes.c_double, vp], ctypes.c_int),
+        "ma_critic_forward_workspace": ([ctypes.POINTER(MAConfig), i32, i32], i64),
+        "ma_critic_forward": ([vp, ctypes.POINTER(MAConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp], ctypes.c_int),
+        "ma_copy_intermediate": ([vp, ctypes.c_int, vp, ctypes.POINTER(i64), vp], ctypes.c_int),
+        "ma_last_plan": ([vp, ctypes.POINTER(MAPlan)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -277,6 +333,30 @@ class ComaHandle:
         try:
             if getattr(self, "h", None) and self.h.value:
                 self.lib.mc_destroy(self.h)
+                self.h = ctypes.c_void_p()
+        except Exception:
+            pass
+
+
+class A2CHandle:
+    """RAII owner of an ma_handle (include/ma_a2c.h)."""
+
+    def __init__(self, cfg: MAConfig):
+        self.lib = load()
+        h = ctypes.c_void_p()
+        check(self.lib.ma_create(ctypes.byref(cfg), ctypes.byref(h)))
+        self.h = h
+        self.cfg = cfg
+        ao = (ctypes.c_int64 * (P_COUNT + 1))()
+        co = (ctypes.c_int64 * (MA_P_COUNT + 1))()
+        check(self.lib.ma_param_offsets(self.h, ao, co))
+        self.agent_offsets = list(ao)
+        self.critic_offsets = list(co)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and self.h.value:
+                self.lib.ma_destroy(self.h)
                 self.h = ctypes.c_void_p()
         except Exception:
             pass

@@ -67,3 +67,19 @@ class EpsilonGreedyActionSelector:
 
 
 REGISTRY["epsilon_greedy"] = EpsilonGreedyActionSelector
+
+
+class SoftPoliciesSelector:
+    """epymarl's soft_policies: sample from the policy BasicMAC.forward returns (softmax, no epsilon floor; the
+    selector has no `epsilon`), argmax in test_mode. The draw stays on torch's RNG."""
+
+    def __init__(self, args):
+        self.args = args
+
+    def select_action(self, agent_inputs, avail_actions, t_env, test_mode=False):
+        if test_mode:
+            return agent_inputs.max(dim=2)[1]
+        return Categorical(agent_inputs).sample().long()
+
+
+REGISTRY["soft_policies"] = SoftPoliciesSelector

@@ -84,7 +84,7 @@ class BasicMAC:
         self.hidden_states = h_out.view(bs, self.n_agents, H)
         if self.agent_output_type == "pi_logits":
             avail = ep_batch["avail_actions"][:, t].to(device=dev, dtype=th.int32).contiguous()
-            eps = float(self.action_selector.epsilon)
+            eps = float(getattr(self.action_selector, "epsilon", 0.0))   # soft_policies has none: no floor
             _lib.check(hd.lib.mc_policy(_lib.ptr(q), _lib.ptr(avail), q.shape[0], q.shape[1], eps,
                                         int(bool(getattr(self.args, "mask_before_softmax", True))),
                                         int(bool(test_mode)), _lib.stream_ptr()))

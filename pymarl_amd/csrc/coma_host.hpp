@@ -106,6 +106,92 @@ int mc_agent_config(const mc_config& c, mq_config* a) {
   return MQ_OK;
 }
 
+// The policy-gradient actor of the COMA and the actor-critic learners (a2c_host.hpp): the agent handle `ah` lends its
+// workspace `w` (w.dHo the caller's), Pa are the agent's parameters, RT = T R the actor's rows.
+//
+// The agent unroll over t < T, online net only: the logits land in w.Q.
+int actor_forward(mq_handle* ah, const Dims& d, const Rep& rpa, const float* Pa, const Lay& L, const Work& w, int64_t RT,
+                  hipStream_t st) {
+  const int rw_fwd = pick_rw(d.R, 512);
+  if (rw_fwd == 1 && fused_fwd_ok(d.I, d.O, d.A, d.n, RT)) {
+    launch_fwd_fused(dim3(d.R, 1), st, d, rpa, Pa, Pa, L, w);
+    MQ_HIP(hipGetLastError());
+  } else {
+    Fc1Prob p1{d, rpa, Pa, Pa, ah->off[MQ_P_FC1_W], ah->off[MQ_P_FC1_B], w.X1, w.XIN, RT};
+    MQ_HIP(launch_gemm(p1, (int)RT, 2 * mq::H, 1, st));
+    GiProb p2{w.X1, Pa, Pa, ah->off[MQ_P_RNN_W_IH], ah->off[MQ_P_RNN_B_IH], w.GI, RT};
+    MQ_HIP(launch_gemm(p2, (int)RT, mq::G3, 1, st));
+    const dim3 grid((d.R + rw_fwd - 1) / rw_fwd, 1);
+    if (rw_fwd == 1) hipLaunchKernelGGL((gru_fwd_kernel<1, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
+    else if (rw_fwd == 2) hipLaunchKernelGGL((gru_fwd_kernel<2, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
+    else if (rw_fwd == 4) hipLaunchKernelGGL((gru_fwd_kernel<4, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
+    else hipLaunchKernelGGL((gru_fwd_kernel<8, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
+    MQ_HIP(hipGetLastError());
+    Fc2Prob p3{w.Hs, Pa, Pa, ah->off[MQ_P_FC2_W], ah->off[MQ_P_FC2_B], w.Q, RT, d.A};
+    MQ_HIP(launch_gemm(p3, (int)RT, d.A, 1, st));
+  }
+  return MQ_OK;
+}
+
+// From the policy kernel's dL [RT][Ap] (dense dLoss/dlogits) and its npol blocks of loss sums `ppart`: BPTT with the
+// dense output gradient, the split-K weight gradients, and the two-pass reduction into agrad [Pa_n | MQ_NSUMS];
+// *nnorm = the norm partials it left in norm_part.
+int actor_backward(mq_handle* ah, const Dims& d, const Rep& rpa, const float* Pa, const Lay& L, const Work& w,
+                   int64_t RT, const float* dL, int Ap, float* slab_fc2, float* ppart, int npol, float* red_tmp,
+                   float* norm_part, float* agrad, int64_t Pa_n, hipStream_t s, int* nnorm) {
+  const int A = d.A;
+  {
+    DhoProb p{dL, Ap, A, Pa + ah->off[MQ_P_FC2_W], w.dHo, RT};
+    MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));
+  }
+  const int rw_bwd = std::min(2, pick_rw(d.R, 256));
+  int nblk_bwd = (d.R + rw_bwd - 1) / rw_bwd;
+  const size_t dyn = ((size_t)2 * d.A * mq::H + d.A) * sizeof(float);
+  if (rw_bwd == 1)
+    hipLaunchKernelGGL((gru_bwd_kernel<1, 0, true>), dim3(nblk_bwd), dim3(512), dyn, s, d, rpa, Pa, L, w, ah->len_rnn);
+  else
+    hipLaunchKernelGGL((gru_bwd_kernel<2, 0, true>), dim3(nblk_bwd), dim3(512), dyn, s, d, rpa, Pa, L, w, ah->len_rnn);
+  MQ_HIP(hipGetLastError());
+  {
+    Dx1Prob p{w.dGI, Pa + ah->off[MQ_P_RNN_W_IH], w.X1, w.dP1, RT};
+    MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));
+  }
+  int ns1;
+  {
+    const int tiles = (d.I + Dw1Prob::BN - 1) / Dw1Prob::BN;
+    int ns = (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RT / 256));
+    ns = std::max(1, std::min(ns, (512 + tiles - 1) / tiles));
+    int64_t chunk = ((RT + ns - 1) / ns + GBK - 1) / GBK * GBK;
+    ns = (int)((RT + chunk - 1) / chunk);
+    ns1 = ns;
+    Dw1Prob p{d.I, w.dP1, w.XIN, w.slab_fc1, RT, ns};
+    MQ_HIP(launch_gemm(p, mq::H, d.I, ns, s));
+  }
+  int ns2;
+  {
+    int ns = (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RT / 256));
+    int64_t chunk = ((RT + ns - 1) / ns + GBK - 1) / GBK * GBK;
+    ns = (int)((RT + chunk - 1) / chunk);
+    ns2 = ns;
+    Dw2Prob p{dL, Ap, A, w.Hs, slab_fc2, RT, ns};
+    MQ_HIP(launch_gemm(p, A, mq::H, ns, s));
+  }
+  RedBuilder rb(red_tmp);
+  rb.add(w.slab_fc1, ns1, (int64_t)mq::H * d.I + mq::H, agrad + ah->off[MQ_P_FC1_W], true);
+  // W_ih .. b_hh: the prefix of each BPTT slab (its fc2 part is unused in the dense-dy mode)
+  rb.add(w.slab_rnn, nblk_bwd, ah->off[MQ_P_FC2_W] - ah->off[MQ_P_RNN_W_IH], agrad + ah->off[MQ_P_RNN_W_IH], true,
+         ah->len_rnn);
+  rb.add(slab_fc2, ns2, (int64_t)A * mq::H + A, agrad + ah->off[MQ_P_FC2_W], true);
+  rb.add(ppart, npol, MQ_NSUMS, agrad + Pa_n, false);
+  hipLaunchKernelGGL(red_pass1_kernel, dim3(rb.b1), dim3(256), 0, s, rb.pl);
+  MQ_HIP(hipGetLastError());
+  if (rb.b2 > 4096) return set_err(MQ_ERR_ARG, "agent too large for the norm partial buffer");
+  hipLaunchKernelGGL(red_pass2_kernel, dim3(rb.b2), dim3(256), 0, s, rb.pl, norm_part);
+  MQ_HIP(hipGetLastError());
+  *nnorm = rb.b2;
+  return MQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -346,27 +432,7 @@ int mc_train_step(mc_handle* h, const mq_replay* batch, float epsilon, void* str
   w.dHo = h->dHo;
   const int64_t RT = (int64_t)T * d.R;   // the actor's rows (its shard under a replicated critic)
   const float* Pa = h->agent;
-  auto agent_forward = [&](hipStream_t st) -> int {
-    const int rw_fwd = pick_rw(d.R, 512);
-    if (rw_fwd == 1 && fused_fwd_ok(d.I, d.O, d.A, d.n, RT)) {
-      launch_fwd_fused(dim3(d.R, 1), st, d, rpa, Pa, Pa, L, w);
-      MQ_HIP(hipGetLastError());
-    } else {
-      Fc1Prob p1{d, rpa, Pa, Pa, ah->off[MQ_P_FC1_W], ah->off[MQ_P_FC1_B], w.X1, w.XIN, RT};
-      MQ_HIP(launch_gemm(p1, (int)RT, 2 * mq::H, 1, st));
-      GiProb p2{w.X1, Pa, Pa, ah->off[MQ_P_RNN_W_IH], ah->off[MQ_P_RNN_B_IH], w.GI, RT};
-      MQ_HIP(launch_gemm(p2, (int)RT, mq::G3, 1, st));
-      const dim3 grid((d.R + rw_fwd - 1) / rw_fwd, 1);
-      if (rw_fwd == 1) hipLaunchKernelGGL((gru_fwd_kernel<1, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-      else if (rw_fwd == 2) hipLaunchKernelGGL((gru_fwd_kernel<2, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-      else if (rw_fwd == 4) hipLaunchKernelGGL((gru_fwd_kernel<4, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-      else hipLaunchKernelGGL((gru_fwd_kernel<8, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-      MQ_HIP(hipGetLastError());
-      Fc2Prob p3{w.Hs, Pa, Pa, ah->off[MQ_P_FC2_W], ah->off[MQ_P_FC2_B], w.Q, RT, d.A};
-      MQ_HIP(launch_gemm(p3, (int)RT, d.A, 1, st));
-    }
-    return MQ_OK;
-  };
+  auto agent_forward = [&](hipStream_t st) -> int { return actor_forward(ah, d, rpa, Pa, L, w, RT, st); };
   // MQ_PLAN coma_overlap=0: the actor's agent unroll stays on the caller's stream
   const bool try_overlap = !dp && !h->timing && plan_int("coma_overlap", 1) != 0 && h->chain_env &&
                            cc_ok(R, A, h->Kc, h->num_cu);
@@ -482,59 +548,11 @@ int mc_train_step(mc_handle* h, const mq_replay* batch, float epsilon, void* str
                      (const float*)h->qvals, R, qv_r0, eps, omeps, (int)(c.mask_before_softmax != 0), h->Ap, h->dL,
                      h->pi, h->ppart);
   MQ_HIP(hipGetLastError());
-  // BPTT with the dense output gradient
-  {
-    DhoProb p{h->dL, h->Ap, A, Pa + ah->off[MQ_P_FC2_W], h->dHo, RT};
-    MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));
-  }
-  const int rw_bwd = std::min(2, pick_rw(d.R, 256));
-  int nblk_bwd = (d.R + rw_bwd - 1) / rw_bwd;
-  const size_t dyn = ((size_t)2 * d.A * mq::H + d.A) * sizeof(float);
-  if (rw_bwd == 1)
-    hipLaunchKernelGGL((gru_bwd_kernel<1, 0, true>), dim3(nblk_bwd), dim3(512), dyn, s, d, rpa, Pa, L, w, ah->len_rnn);
-  else
-    hipLaunchKernelGGL((gru_bwd_kernel<2, 0, true>), dim3(nblk_bwd), dim3(512), dyn, s, d, rpa, Pa, L, w, ah->len_rnn);
-  MQ_HIP(hipGetLastError());
-  {
-    Dx1Prob p{w.dGI, Pa + ah->off[MQ_P_RNN_W_IH], w.X1, w.dP1, RT};
-    MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));
-  }
-  int ns1;
-  {
-    const int tiles = (d.I + Dw1Prob::BN - 1) / Dw1Prob::BN;
-    int ns = (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RT / 256));
-    ns = std::max(1, std::min(ns, (512 + tiles - 1) / tiles));
-    int64_t chunk = ((RT + ns - 1) / ns + GBK - 1) / GBK * GBK;
-    ns = (int)((RT + chunk - 1) / chunk);
-    ns1 = ns;
-    Dw1Prob p{d.I, w.dP1, w.XIN, w.slab_fc1, RT, ns};
-    MQ_HIP(launch_gemm(p, mq::H, d.I, ns, s));
-  }
-  int ns2;
-  {
-    int ns = (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RT / 256));
-    int64_t chunk = ((RT + ns - 1) / ns + GBK - 1) / GBK * GBK;
-    ns = (int)((RT + chunk - 1) / chunk);
-    ns2 = ns;
-    Dw2Prob p{h->dL, h->Ap, A, w.Hs, h->slab_fc2, RT, ns};
-    MQ_HIP(launch_gemm(p, A, mq::H, ns, s));
-  }
+  // BPTT with the dense output gradient, the weight gradients and their reduction
   int nnorm;
-  {
-    RedBuilder rb(h->red_tmp);
-    rb.add(w.slab_fc1, ns1, (int64_t)mq::H * d.I + mq::H, h->agrad + ah->off[MQ_P_FC1_W], true);
-    // W_ih .. b_hh: the prefix of each BPTT slab (its fc2 part is unused in the dense-dy mode)
-    rb.add(w.slab_rnn, nblk_bwd, ah->off[MQ_P_FC2_W] - ah->off[MQ_P_RNN_W_IH], h->agrad + ah->off[MQ_P_RNN_W_IH],
-           true, ah->len_rnn);
-    rb.add(h->slab_fc2, ns2, (int64_t)A * mq::H + A, h->agrad + ah->off[MQ_P_FC2_W], true);
-    rb.add(h->ppart, npol, MQ_NSUMS, h->agrad + h->Pa, false);
-    hipLaunchKernelGGL(red_pass1_kernel, dim3(rb.b1), dim3(256), 0, s, rb.pl);
-    MQ_HIP(hipGetLastError());
-    if (rb.b2 > 4096) return set_err(MQ_ERR_ARG, "agent too large for the norm partial buffer");
-    hipLaunchKernelGGL(red_pass2_kernel, dim3(rb.b2), dim3(256), 0, s, rb.pl, h->norm_part);
-    MQ_HIP(hipGetLastError());
-    nnorm = rb.b2;
-  }
+  if ((rc = actor_backward(ah, d, rpa, Pa, L, w, RT, h->dL, h->Ap, h->slab_fc2, h->ppart, npol, h->red_tmp,
+                           h->norm_part, h->agrad, h->Pa, s, &nnorm)))
+    return rc;
   if (repl && chained) {   // the chain's error word rides in the agent sums' spare slot 7 (0 on success)
     hipLaunchKernelGGL(coma_halt_to_sum_kernel, dim3(1), dim3(64), 0, s, (const int*)(h->cstate + 3),
                        h->agrad + h->Pa + 7);

@@ -29,7 +29,8 @@
 // The host side by file: host_util.hpp (errors, HIP / LDS checks, device-buffer owner, workspace table),
 // learner_layout.hpp (parameter layout and workspace sizes from the config), step_plan.hpp and reduce_plan.hpp (what a
 // step launches, decided without a HIP call), learner_handle.hpp (mq_handle, batch checks), step_launch.hpp (the
-// launches), optim_host.hpp (Adam's host side), coma_host.hpp (the COMA learner). This file holds the C ABI.
+// launches), optim_host.hpp (Adam's host side), coma_host.hpp (the COMA learner), a2c_host.hpp (the actor-critic learner, with
+// a2c_plan.hpp and a2c_kernels.hpp). This file holds the C ABI.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -39,6 +40,7 @@
 #include "module_fwd.hpp"
 #include "optim_host.hpp"
 #include "coma_host.hpp"
+#include "a2c_host.hpp"
 
 namespace {
 

@@ -5,8 +5,9 @@
 
 Pulls the gfx950 code object out of each library's .hip_fatbin section, disassembles it, and compares every function
 symbol of OLD with the symbol of the same name in NEW: the instruction text and the encoded words, addresses removed
-(branches are relative, so a kernel that merely moved compares equal), and every kernel's metadata entry (argument
-block, registers, LDS, scratch). Prints one JSON line: how many symbols were identical, which differ, which are
+(branches are relative, so a kernel that merely moved compares equal; the s_nop padding behind a function's
+terminating s_endpgm / s_setpc is dropped: it depends on what follows the function), and every kernel's metadata entry
+(argument block, registers, LDS, scratch). Prints one JSON line: how many symbols were identical, which differ, which are
 missing from NEW, whose metadata differs, and which NEW adds. Exit status 1 if any OLD symbol is missing or differs.
 Needs no GPU.
 """
@@ -49,6 +50,15 @@ def functions(co, llvm):
             continue
         ins, enc = line.split("//", 1)
         cur.append(ins.strip() + " | " + enc.split(":", 1)[1].strip())   # drop the address before the encoding
+    # the s_nop padding behind a function's terminating s_endpgm / s_setpc depends on what the linker placed after it
+    # (the last function of the section is padded to the section's end): not part of the function. Nothing but such
+    # padding is dropped: nops anywhere before the terminator stay.
+    for body in out.values():
+        n = len(body)
+        while n and body[n - 1].startswith("s_nop 0 |"):
+            n -= 1
+        if n and n < len(body) and body[n - 1].startswith(("s_endpgm", "s_setpc")):
+            del body[n:]
     return out
 
 

@@ -1,0 +1,523 @@
+"""An independent restatement of one ActorCriticLearner.train(), in torch on the CPU with autograd.
+
+`a2c_ref_step(case, state, batch, dtype)` runs the whole step in float64 or in float32: the critic inputs (cv: state |
+last joint one-hot actions | agent id; ac: obs | agent id), V' of the target critic over every stored step, V of the
+critic over t < T, reward standardisation with running statistics, the n-step return as the specification's Python
+loops, the masked L2 critic loss, autograd, clip_grad_norm_ and a real torch.optim step; then the agent unroll (fc1 ->
+relu -> GRU cell -> fc2), the softmax policy (unavailable actions at -1e10 first under mask_before_softmax, no epsilon
+floor), pi = 1 on dead rows, the entropy, the policy-gradient loss, autograd, clip and a real torch.optim step. It
+shares no hand-derived backward with the kernels (pymarl_amd/csrc/a2c_kernels.hpp).
+
+The float32 run of the same function gives `e32`, each block's fp32 error against the float64 run from the same state;
+the gate is tests/ref64.py's min(1e-5, 16 max(e32, 2e-7)) over `blocks(case)`: every critic tensor, fc1.weight also by
+input kind, and ref64.grad_blocks' split of the agent tensors.
+
+The relus cannot be read back from the kernels: `kink_minima` is the smallest |pre-activation| over live (mask = 1)
+rows of the critic's two relus and of the agent's fc1 relu, and a row of ROWS is only valid with a seed that keeps them
+above the row's margin at both steps. `python -m tests.a2c_ref` searches the seeds (0, 1, ..: the first whose minima
+exceed twice the margin at step 0 and, with the float32 run's own update standing in for the GPU's, at step 1).
+"""
+from __future__ import annotations
+
+from collections import OrderedDict
+from types import SimpleNamespace
+
+import numpy as np
+import torch as th
+
+from pymarl_amd.utils.synthetic import agent_param_shapes, init_params, make_replay
+from tests import ref64
+
+H = 64
+F32, F64 = th.float32, th.float64
+MARGIN = ref64.KINK_EPS
+REW_MS_INIT = (0.0, 1.0, 1e-4)
+STATS = ["critic_loss", "critic_grad_norm", "td_error_abs", "q_taken_mean", "target_mean", "advantage_mean",
+         "pg_loss", "agent_grad_norm", "pi_max"]
+
+# The rows of tests/test_gpu_a2c.py: t_len stored slots (T = t_len - 1), `lengths` the episodes' lengths (an episode of
+# length L < T terminated at L - 1; 0: an empty episode, nothing filled). Each is the smallest shape at which its edge
+# exists; `over` are the learner keys that differ from DEFAULTS. `seed`: see the module docstring (split keeps all
+# but one episode short: 35k pre-activations per relu of 544 live rows leave no seed in 0..63 above the margin).
+_PART = dict(n=3, A=5, t_len=7, S=7, O=5, B=3, lengths=(6, 3, 0))
+ROWS = OrderedDict([
+    ("one", dict(n=1, A=2, t_len=3, S=3, O=3, B=1, lengths=(2,), seed=0)),
+    ("part", dict(_PART, seed=0)),
+    ("rows9", dict(n=3, A=5, t_len=4, S=7, O=5, B=1, lengths=(3,), seed=1)),
+    ("A33", dict(_PART, A=33, seed=2)),
+    ("A64", dict(_PART, A=64, seed=0)),
+    ("split", dict(n=4, A=5, t_len=18, S=7, O=5, B=8, lengths=(17, 2, 1, 3, 1, 2, 1, 1), seed=30)),
+    ("wide", dict(_PART, seed=0, over=dict(hidden_dim=128))),
+    # `part` over the keys, paired up: each value of each key runs at least once
+    ("part_ac", dict(_PART, seed=2, over=dict(critic_type="ac_critic", obs_last_action=False, mask_before_softmax=False,
+                                             q_nstep=1, add_value_last_step=False, entropy_coef=0.0,
+                                             optimizer="rmsprop", standardise_rewards=True))),
+    ("part_n10", dict(_PART, seed=0, over=dict(obs_last_action=False, q_nstep=10, optimizer="rmsprop",
+                                              standardise_rewards=True))),
+    ("part_ac_adam", dict(_PART, seed=2, over=dict(critic_type="ac_critic", mask_before_softmax=False,
+                                                  add_value_last_step=False, entropy_coef=0.0))),
+])
+DEFAULTS = dict(critic_type="cv_critic", obs_last_action=True, obs_agent_id=True, mask_before_softmax=True, q_nstep=5,
+                add_value_last_step=True, entropy_coef=0.01, optimizer="adam", standardise_rewards=False,
+                hidden_dim=64, lr=5e-4, gamma=0.99, grad_norm_clip=10.0, optim_alpha=0.99, optim_eps=1e-5)
+
+
+def critic_shapes(K, Hc):
+    return OrderedDict([("fc1.weight", (Hc, K)), ("fc1.bias", (Hc,)), ("fc2.weight", (Hc, Hc)), ("fc2.bias", (Hc,)),
+                        ("fc3.weight", (1, Hc)), ("fc3.bias", (1,))])
+
+
+def set_lengths(data, lengths):
+    """The replay contract of pymarl_amd/utils/synthetic.py applied to given episode lengths, in place."""
+    Tp = data["filled"].shape[1]
+    T = Tp - 1
+    data["terminated"][:] = 0
+    data["filled"][:] = 1
+    for e, L in enumerate(lengths):
+        L = int(L)
+        if L == 0:   # an empty episode: no slot was ever written
+            for k in data:
+                data[k][e] = 0
+            continue
+        if L < T or e % 2 == 0:
+            data["terminated"][e, L - 1, 0] = 1
+        data["reward"][e, L:] = 0.0
+        if L + 1 < Tp:
+            for k in ("obs", "state", "avail_actions", "actions", "actions_onehot"):
+                data[k][e, L + 1:] = 0
+            data["filled"][e, L + 1:] = 0
+    return data
+
+
+class A2CCase:
+    """Replay, weights and learner keys of one row, from `seed` (n_episodes = B: every step trains episodes 0..B-1)."""
+
+    def __init__(self, row, seed=None):
+        d = ROWS[row]
+        self.row = row
+        self.keys = dict(DEFAULTS, **d.get("over", {}))
+        self.n, self.A, self.O, self.S, self.B = d["n"], d["A"], d["O"], d["S"], d["B"]
+        self.T = d["t_len"] - 1   # the storage's episode_limit
+        self.n_episodes, self.steps = self.B, 2
+        self.seed = d["seed"] if seed is None else seed
+        self.data = set_lengths(make_replay(self.B, self.T, self.n, self.A, self.O, self.S, seed=self.seed),
+                                d["lengths"])
+        self.obs_last_action, self.obs_agent_id = bool(self.keys["obs_last_action"]), True
+        self.mixer, self.mixer_shapes = "none", OrderedDict()
+        self.I = self.O + (self.A if self.obs_last_action else 0) + self.n
+        self.cv = self.keys["critic_type"] == "cv_critic"
+        self.K = (self.S + (self.n * self.A if self.obs_last_action else 0) + self.n) if self.cv else self.O + self.n
+        self.Hc = self.keys["hidden_dim"]
+        self.agent_shapes = agent_param_shapes(self.I, H, self.A)
+        self.critic_shapes = critic_shapes(self.K, self.Hc)
+        self.agent_params = init_params(self.agent_shapes, seed=self.seed + 1)
+        self.critic_params = init_params(self.critic_shapes, seed=self.seed + 201)
+        self.gpow = np.array([float(self.keys["gamma"]) ** k for k in range(self.keys["q_nstep"] + 2)], np.float32)
+
+    def batch(self):
+        """The numpy batch every step trains on: all episodes, truncated to the longest one's filled slots."""
+        max_t = int(self.data["filled"].sum(1).max())
+        return OrderedDict((k, v[:, :max_t]) for k, v in self.data.items())
+
+    def views(self):
+        return _View(self, self.agent_shapes, True), _View(self, self.critic_shapes, False)
+
+    def init_state(self):
+        """The learner's state before the first train(): flat float32 parameters, zero moments, step 0."""
+        a = np.concatenate([v.ravel() for v in self.agent_params.values()])
+        c = np.concatenate([v.ravel() for v in self.critic_params.values()])
+        z = np.zeros_like
+        return dict(agent=a, critic=c, target=c.copy(), a_m=z(a), a_v=z(a), c_m=z(c), c_v=z(c), step=0,
+                    rew_ms=REW_MS_INIT)
+
+
+class _View:
+    """What ref64.grad_blocks / block_errors read of a case, over one flat parameter vector."""
+
+    def __init__(self, case, shapes, agent):
+        self.n, self.A, self.O = case.n, case.A, case.O
+        self.agent_shapes = shapes if agent else OrderedDict()
+        self.mixer_shapes = OrderedDict() if agent else shapes
+        self.obs_last_action, self.obs_agent_id = case.obs_last_action, True
+        self.mixer = "none"
+
+    def unflatten(self, flat):
+        out, o = OrderedDict(), 0
+        for k, s in list(self.agent_shapes.items()) + list(self.mixer_shapes.items()):
+            sz = int(np.prod(s))
+            out[k] = flat[o:o + sz].reshape(s)
+            o += sz
+        return out
+
+
+def blocks(case):
+    """{"critic": blocks, "agent": blocks}, each {block name: (tensor name, index)}."""
+    full = slice(None)
+    critic = OrderedDict((k, (k, (full,))) for k in case.critic_shapes)
+    if case.cv:
+        kinds = [("state", case.S)] + ([("last_actions", case.n * case.A)] if case.obs_last_action else [])
+    else:
+        kinds = [("obs", case.O)]
+    o = 0
+    for kind, w in kinds + [("agent_id", case.n)]:
+        critic["fc1.weight[{}]".format(kind)] = ("fc1.weight", (full, slice(o, o + w)))
+        o += w
+    assert o == case.K
+    return dict(critic=critic, agent=ref64.grad_blocks(case.views()[0]))
+
+
+def critic_inputs(case, batch, dt):
+    """(B, Tp, n, K), a dense construction of its own (the modules' build_inputs is tested against it)."""
+    t = lambda a: th.tensor(np.asarray(a, np.float64), dtype=dt)  # noqa: E731
+    B, Tp = batch["filled"].shape[:2]
+    n = case.n
+    eye = th.eye(n, dtype=dt).expand(B, Tp, n, n)
+    if not case.cv:
+        return th.cat([t(batch["obs"]), eye], -1)
+    parts = [t(batch["state"]).unsqueeze(2).expand(B, Tp, n, case.S)]
+    if case.obs_last_action:
+        oh = t(batch["actions_onehot"]) * t(batch["filled"]).unsqueeze(2)
+        last = th.cat([th.zeros_like(oh[:, :1]), oh[:, :-1]], 1).reshape(B, Tp, 1, n * case.A)
+        parts.append(last.expand(B, Tp, n, n * case.A))
+    return th.cat(parts + [eye], -1)
+
+
+def nstep_loop(Vt, r, m, g, N, add_last):
+    """Step 3 of the specification as written. Vt (B, T + 1, n), r / m (B, T, 1), g the fp32 table: (B, T, n)."""
+    T = r.shape[1]
+    ret = th.zeros_like(Vt[:, :T])
+    gs = [th.tensor(float(x), dtype=Vt.dtype) for x in g]
+    for t0 in range(T):
+        acc = th.zeros_like(Vt[:, 0])
+        for s in range(N + 1):
+            t = t0 + s
+            if t >= T:
+                break
+            if s == N:
+                acc = acc + (gs[s] * Vt[:, t]) * m[:, t]
+            elif t == T - 1 and add_last:
+                acc = acc + (gs[s] * r[:, t]) * m[:, t]
+                acc = acc + gs[s + 1] * Vt[:, t + 1]
+            else:
+                acc = acc + (gs[s] * r[:, t]) * m[:, t]
+        ret[:, t0] = acc
+    return ret
+
+
+def nstep_elem(Vt, r, m, g, N, add_last):
+    """The same return one element at a time in numpy float32 scalars: the kernel's form (a thread per (b, agent, t0),
+    every product and sum rounded to fp32). Bitwise nstep_loop's float32 result."""
+    Vt, r, m = (np.asarray(a, np.float32) for a in (Vt, r, m))
+    B, Tp, n = Vt.shape
+    T = Tp - 1
+    g = np.asarray(g, np.float32)
+    ret = np.zeros((B, T, n), np.float32)
+    for b in range(B):
+        for ag in range(n):
+            for t0 in range(T):
+                acc = np.float32(0.0)
+                for s in range(N + 1):
+                    t = t0 + s
+                    if t >= T:
+                        break
+                    if s == N:
+                        acc = np.float32(acc + np.float32(np.float32(g[s] * Vt[b, t, ag]) * m[b, t, 0]))
+                    else:
+                        acc = np.float32(acc + np.float32(np.float32(g[s] * r[b, t, 0]) * m[b, t, 0]))
+                        if t == T - 1 and add_last:
+                            acc = np.float32(acc + np.float32(g[s + 1] * Vt[b, t + 1, ag]))
+                ret[b, t0, ag] = acc
+    return ret
+
+
+def reward_merge(x, ms):
+    """Running (mean, var, count) merged with the batch x (all its values, float64): DESIGN.md §3i."""
+    mean, var, count = (float(v) for v in ms)
+    x = np.asarray(x, np.float64).ravel()
+    M = x.size
+    bm = x.sum() / M
+    bv = ((x - bm) ** 2).sum() / (M - 1) if M > 1 else 0.0
+    delta, tot = bm - mean, count + M
+    return (mean + delta * M / tot, (var * count + bv * M + delta * delta * count * M / tot) / tot, tot)
+
+
+def policy_terms(logits, avail, actions, m, adv, ec, mbs):
+    """pi (the softmax policy), and the loss sum -sum((adv log(pi_u + 1e-10) + ec H) m) over rows, before / M."""
+    lg = logits.masked_fill(avail == 0, -1e10) if mbs else logits
+    p = th.softmax(lg, -1)
+    pi = th.where(m.unsqueeze(-1) == 0, th.ones_like(p), p)
+    ent = -(pi * th.log(pi + 1e-10)).sum(-1)
+    pi_u = th.gather(pi, -1, actions).squeeze(-1)
+    num = -((adv * th.log(pi_u + 1e-10) + ec * ent) * m).sum()
+    return p, pi, ent, num
+
+
+def logit_formula(p, avail, actions, m, adv, ec, mbs, M):
+    """Step 5's hand-derived dLoss/dlogits (the kernel's form, here with the 1 / M scale), for the CPU test against
+    autograd: g_j = -(m / M) [adv [j == u] / (p_j + 1e-10) - ec (log(p_j + 1e-10) + p_j / (p_j + 1e-10))],
+    dlogit_k = p_k (g_k - sum_j p_j g_j), zero at masked-before-softmax actions and on dead rows."""
+    onehot = th.zeros_like(p).scatter_(-1, actions, 1.0)
+    den = p + 1e-10
+    g = -(m / M).unsqueeze(-1) * (adv.unsqueeze(-1) * onehot / den - ec * (th.log(den) + p / den))
+    dl = p * (g - (p * g).sum(-1, keepdim=True))
+    dl = dl * (m.unsqueeze(-1) != 0)
+    return dl.masked_fill(avail == 0, 0.0) if mbs else dl
+
+
+def _unroll(p, obs, onehot, filled, flags, dt):
+    """BasicMAC.forward over t with RNNAgent: logits (B, T, n, A) and the fc1 pre-activations (B, T, n, H)."""
+    B, T, n, _ = obs.shape
+    A = onehot.shape[-1]
+    eye = th.eye(n, dtype=dt).expand(B, n, n)
+    h = th.zeros(B * n, H, dtype=dt)
+    outs, pres = [], []
+    for t in range(T):
+        parts = [obs[:, t]]
+        if flags[0]:
+            parts.append(th.zeros(B, n, A, dtype=dt) if t == 0 else onehot[:, t - 1] * filled[:, t - 1].unsqueeze(-1))
+        if flags[1]:
+            parts.append(eye)
+        x = th.cat(parts, -1).reshape(B * n, -1)
+        pre = x @ p["fc1.weight"].T + p["fc1.bias"]
+        pres.append(pre.reshape(B, n, H))
+        x1 = th.relu(pre)
+        gi = x1 @ p["rnn.weight_ih"].T + p["rnn.bias_ih"]
+        gh = h @ p["rnn.weight_hh"].T + p["rnn.bias_hh"]
+        r = th.sigmoid(gi[:, :H] + gh[:, :H])
+        z = th.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+        c = th.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
+        h = (1.0 - z) * c + z * h
+        outs.append((h @ p["fc2.weight"].T + p["fc2.bias"]).reshape(B, n, A))
+    return th.stack(outs, 1), th.stack(pres, 1)
+
+
+def _params(view, flat, dt):
+    return OrderedDict((k, th.nn.Parameter(th.tensor(np.asarray(v, np.float64), dtype=dt)))
+                       for k, v in view.unflatten(np.asarray(flat)).items())
+
+
+def _optim_step(case, view, P, clipped, m_flat, v_flat, step, dt):
+    """A real torch.optim step on P from the given moments; returns (new params, new exp_avg or None, new second
+    moment), flat float64."""
+    k = case.keys
+    ps = list(P.values())
+    adam = k["optimizer"] == "adam"
+    opt = th.optim.Adam(ps, lr=k["lr"]) if adam else th.optim.RMSprop(ps, lr=k["lr"], alpha=k["optim_alpha"],
+                                                                      eps=k["optim_eps"])
+    mom = lambda flat: [th.tensor(np.asarray(v, np.float64), dtype=dt)   # noqa: E731
+                        for v in view.unflatten(np.asarray(flat)).values()]
+    ms, vs = mom(m_flat), mom(v_flat)
+    for p, g, m_, v_ in zip(ps, clipped.values(), ms, vs):
+        p.grad = g.to(dt)
+        st = dict(step=th.tensor(float(step)))
+        if adam:
+            st["exp_avg"], st["exp_avg_sq"] = m_, v_
+        else:
+            st["square_avg"] = v_
+        opt.state[p] = st
+    opt.step()
+    flat = lambda ts: np.concatenate([t.detach().double().numpy().ravel() for t in ts])   # noqa: E731
+    return (flat(ps), flat([opt.state[p]["exp_avg"] for p in ps]) if adam else None,
+            flat([opt.state[p]["exp_avg_sq" if adam else "square_avg"] for p in ps]))
+
+
+def _clip(P, max_norm):
+    grads = OrderedDict((k, p.grad.detach().clone()) for k, p in P.items())
+    norm = float(th.sqrt(sum((g.double() ** 2).sum() for g in grads.values())))
+    coef = min(max_norm / (norm + 1e-6), 1.0)
+    return norm, OrderedDict((k, g * coef) for k, g in grads.items())
+
+
+def a2c_ref_step(case, state, batch, dtype=F64, Vt_override=None):
+    """One train() from `state` (A2CCase.init_state's layout) on the numpy `batch`, in `dtype`.
+    Vt_override (B, T + 1, n): V' to form the returns from in place of this run's own (the bitwise gate of the returns).
+    Returns a namespace; every array float64 numpy unless said otherwise: Vt, V, ret, pi, dlogits (d pg_loss /
+    dlogits, with the 1 / M scale), mask (B, T, 1), M, stats, critic_grads / agent_grads (clipped, flat),
+    critic_norm / agent_norm, new (the state after the step, same layout), kink_minima, live (M > 0)."""
+    k, dt = case.keys, dtype
+    n, A = case.n, case.A
+    av, cv = case.views()
+    t = lambda a: th.tensor(np.asarray(a, np.float64), dtype=dt)  # noqa: E731
+    Tp = batch["filled"].shape[1]
+    T = Tp - 1
+    filled, term = t(batch["filled"]), t(batch["terminated"])
+    m = filled[:, :T].clone()
+    m[:, 1:] = m[:, 1:] * (1.0 - term[:, :T - 1])
+    mn = m.expand(-1, -1, n)
+    M = float(mn.sum())
+    # 1. rewards
+    r = t(batch["reward"][:, :T])
+    rew_ms = tuple(state["rew_ms"])
+    if k["standardise_rewards"]:
+        rew_ms = reward_merge(batch["reward"][:, :T], rew_ms)
+        r = (r - t(rew_ms[0])) / th.sqrt(t(rew_ms[1]))
+    # 2. critics
+    Pc, Pt = _params(cv, state["critic"], dt), _params(cv, state["target"], dt)
+    X = critic_inputs(case, batch, dt)
+
+    def critic(P, x):
+        z1 = x @ P["fc1.weight"].T + P["fc1.bias"]
+        z2 = th.relu(z1) @ P["fc2.weight"].T + P["fc2.bias"]
+        return z1, z2, (th.relu(z2) @ P["fc3.weight"].T + P["fc3.bias"]).squeeze(-1)
+    with th.no_grad():
+        Vt = critic(Pt, X)[2]
+    z1, z2, V = critic(Pc, X[:, :T])
+    # 3. returns
+    src = Vt if Vt_override is None else t(Vt_override)
+    ret = nstep_loop(src, r, m, case.gpow, k["q_nstep"], k["add_value_last_step"])
+    # 4. critic loss
+    td = (ret.detach() - V) * mn
+    live = M > 0
+    new = dict(state, rew_ms=rew_ms)
+    out = SimpleNamespace(Vt=Vt.double().numpy(), V=V.detach().double().numpy(), ret=ret.double().numpy(),
+                          mask=m.double().numpy(), M=M, live=live, new=new)
+    if not live:
+        return out
+    critic_loss = (td ** 2).sum() / M
+    critic_loss.backward()
+    cnorm, cclip = _clip(Pc, k["grad_norm_clip"])
+    # 5. actor
+    Pa = _params(av, state["agent"], dt)
+    logits, pre = _unroll(Pa, t(batch["obs"][:, :T]), t(batch["actions_onehot"][:, :T]), filled[:, :T],
+                          (case.obs_last_action, True), dt)
+    logits.retain_grad()
+    avail = th.tensor(np.asarray(batch["avail_actions"][:, :T]))
+    actions = th.tensor(np.asarray(batch["actions"][:, :T], np.int64))
+    adv = td.detach()
+    p, pi, ent, num = policy_terms(logits, avail, actions, mn, adv, k["entropy_coef"], k["mask_before_softmax"])
+    pg_loss = num / M
+    pg_loss.backward()
+    anorm, aclip = _clip(Pa, k["grad_norm_clip"])
+    step = int(state["step"]) + 1
+    c_new, c_m, c_v = _optim_step(case, cv, Pc, cclip, state["c_m"], state["c_v"], step - 1, dt)
+    a_new, a_m, a_v = _optim_step(case, av, Pa, aclip, state["a_m"], state["a_v"], step - 1, dt)
+    new.update(agent=a_new, critic=c_new, a_v=a_v, c_v=c_v, step=step)
+    if a_m is not None:
+        new.update(a_m=a_m, c_m=c_m)
+    flat = lambda d: np.concatenate([g.double().numpy().ravel() for g in d.values()])   # noqa: E731
+    lv = (mn > 0)
+    with th.no_grad():
+        stats = dict(critic_loss=critic_loss.item(), critic_grad_norm=cnorm, td_error_abs=td.abs().sum().item() / M,
+                     q_taken_mean=(V * mn).sum().item() / M, target_mean=(ret * mn).sum().item() / M,
+                     advantage_mean=(adv * mn).sum().item() / M, pg_loss=pg_loss.item(), agent_grad_norm=anorm,
+                     pi_max=(pi.max(-1)[0] * mn).sum().item() / M)
+        kinks = dict(critic_fc1=float(z1.abs()[lv].min()), critic_fc2=float(z2.abs()[lv].min()),
+                     agent_fc1=float(pre.abs()[lv].min()))
+    out.__dict__.update(pi=p.detach().double().numpy(), dlogits=logits.grad.double().numpy(), stats=stats,
+                        critic_grads=flat(cclip), agent_grads=flat(aclip), critic_norm=cnorm, agent_norm=anorm,
+                        kink_minima=kinks, td=td.detach().double().numpy())
+    return out
+
+
+QUANTITIES = ("cgrad", "agrad", "c_v", "a_v", "c_m", "a_m")
+DELTA_CAP = 1e-3   # a parameter update: a wrong sign or a dropped row moves it by O(1) of its block
+
+
+def quantities(r):
+    """{quantity: flat float64} of a reference step `r`: both clipped gradients and both optimisers' moments after the
+    step (no first moment under RMSprop)."""
+    q = dict(cgrad=r.critic_grads, agrad=r.agent_grads, c_v=r.new["c_v"], a_v=r.new["a_v"])
+    if r.new.get("a_m") is not None and np.any(r.new["a_m"]):
+        q.update(c_m=r.new["c_m"], a_m=r.new["a_m"])
+    return q
+
+
+def judge(case, r64, r32, got):
+    """The gate on one train(): `got` {quantity: flat vector} of the implementation under test, r64 / r32 the reference
+    in float64 / float32 from the same state: gradients and moments per block under ref64's rule
+    min(1e-5, 16 max(e32, 2e-7)). Returns ({quantity: {block: dict(err, e32, tol, ratio)}},
+    [(quantity, block, err, tol) over tolerance])."""
+    bl = blocks(case)
+    av, cv = case.views()
+    ref, o32 = quantities(r64), quantities(r32)
+    rec, bad = OrderedDict(), []
+    for q in QUANTITIES:
+        if q not in ref:
+            continue
+        view, b = (av, bl["agent"]) if q.startswith("a") else (cv, bl["critic"])
+        named = view.unflatten(ref[q])
+        e32 = ref64.block_errors(o32[q], named, view, b)
+        errs = ref64.block_errors(got[q], named, view, b)
+        tol, ratio = ref64.tolerances(e32), ref64.ratios(errs, e32)
+        rec[q] = OrderedDict((x, dict(err=errs[x], e32=e32[x], tol=tol[x], ratio=ratio[x])) for x in errs)
+        bad += [(q, x, e, t) for x, (e, t) in ref64.failures(errs, tol).items()]
+    return rec, bad
+
+
+def judge_updates(case, before, got_grads, after):
+    """Both parameter updates p_after - p_before per block. An optimiser's update is not a well-conditioned function of
+    the gradient where |g| is of the size of its eps (Adam: d update / dg = lr eps / (|g| + eps)^2, a 1e-10 error of
+    a 1e-8 gradient element moves its update by 1e-3 lr), so it is not judged against the reference's gradient: the
+    reference here is a real torch.optim step in float64 from the state `before` on the implementation's OWN clipped
+    gradient (got_grads = dict(agent, critic), each gated against the reference by `judge`). What is left is the
+    fp32 evaluation of the update and the fp32 storage of the parameters:
+    tol = min(1e-3, 16 max(2e-7, 2^-24 max|p| / max|update|)) per block, on the scale of the block's max|update|; the
+    cap is tests/coma_ref64.py's DELTA_CAP: a gross apply error on a block whose update is tiny beside its parameters
+    cannot hide behind the floor."""
+    bl = blocks(case)
+    av, cv = case.views()
+    rec, bad = OrderedDict(), []
+    for who, view, b, mk, vk in (("critic", cv, bl["critic"], "c_m", "c_v"), ("agent", av, bl["agent"], "a_m", "a_v")):
+        P = _params(view, before[who], F64)
+        g = OrderedDict((k, th.tensor(np.asarray(v, np.float64))) for k, v in view.unflatten(
+            np.asarray(got_grads[who], np.float64)).items())
+        new, _, _ = _optim_step(case, view, P, g, before[mk], before[vk], int(before["step"]), F64)
+        p0 = np.asarray(before[who], np.float64)
+        ref = view.unflatten(new - p0)
+        got = np.asarray(after[who], np.float64) - p0
+        errs = ref64.block_errors(got, ref, view, b)
+        pk = view.unflatten(p0)
+        out = OrderedDict()
+        for name, (t, idx) in b.items():
+            fl = 2.0 ** -24 * float(np.abs(pk[t][idx]).max()) / max(float(np.abs(ref[t][idx]).max()), 1e-300)
+            tol = min(DELTA_CAP, ref64.TOL_ROOM * max(ref64.E32_FLOOR, fl))
+            out[name] = dict(err=errs[name], e32=0.0, tol=tol, ratio=errs[name] / (tol / ref64.TOL_ROOM))
+            if not errs[name] <= tol:
+                bad.append((who + "_delta", name, errs[name], tol))
+        rec[who + "_delta"] = out
+    return rec, bad
+
+
+def worst(rec):
+    return max(((q, b, v["ratio"]) for q, d in rec.items() for b, v in d.items()), key=lambda x: x[2])
+
+
+def to32(state):
+    """A state as the learner's float32 buffers would hold it (the stand-in for the GPU's state in the seed search)."""
+    f = lambda v: np.asarray(v, np.float32) if isinstance(v, np.ndarray) else v   # noqa: E731
+    return {k: f(v) for k, v in state.items()}
+
+
+def seed_minima(row, seed):
+    """min over both steps of the three kink minima of `row` at `seed` (step 1 from the float32 run's own update)."""
+    c = A2CCase(row, seed)
+    b, st, lo = c.batch(), c.init_state(), {}
+    for _ in range(2):
+        r = a2c_ref_step(c, st, b, F64)
+        for name, v in r.kink_minima.items():
+            lo[name] = min(lo.get(name, np.inf), v)
+        st = to32(a2c_ref_step(c, st, b, F32).new)
+    return lo
+
+
+def lo32_bad(row, seed):
+    """The float32 run's own misses of the gate at both steps (a block whose e32 is above the cap: no seed for a row)."""
+    c = A2CCase(row, seed)
+    b, st, bad = c.batch(), c.init_state(), []
+    for _ in range(2):
+        r64, r32 = a2c_ref_step(c, st, b, F64), a2c_ref_step(c, st, b, F32)
+        bad += judge(c, r64, r32, quantities(r32))[1]
+        bad += judge_updates(c, st, dict(agent=r32.agent_grads, critic=r32.critic_grads), r32.new)[1]
+        st = to32(r32.new)
+    return bad
+
+
+if __name__ == "__main__":
+    for row in ROWS:
+        for seed in range(64):
+            lo = seed_minima(row, seed)
+            if min(lo.values()) > 2 * MARGIN and not lo32_bad(row, seed):
+                print("{}: seed {} (minima {})".format(row, seed, {a: "{:.3g}".format(v) for a, v in lo.items()}))
+                break
+        else:
+            print("{}: no seed in 0..63".format(row))
