@@ -1,18 +1,11 @@
 """Build the actor-critic learner on a tests/a2c_ref.py case (same data and weights as the reference's state)."""
 from __future__ import annotations
 
-import logging
 from types import SimpleNamespace as SN
 
 import numpy as np
-import torch as th
 
-from pymarl_amd.components.episode_buffer import ReplayBuffer
-from pymarl_amd.components.transforms import OneHot
-from pymarl_amd.controllers import REGISTRY as mac_REGISTRY
-from pymarl_amd.learners import REGISTRY as le_REGISTRY
-from pymarl_amd.utils.logging import Logger
-from tests.gpu_helpers import make_scheme
+from tests.gpu_helpers import build_learner, load_actor_critic
 
 
 def make_a2c_args(case, **over):
@@ -31,21 +24,9 @@ def make_a2c_args(case, **over):
 
 
 def build_a2c(case, device="cuda", data=None, **over):
-    args = make_a2c_args(case, **over)
-    groups = {"agents": case.n}
-    preprocess = {"actions": ("actions_onehot", [OneHot(out_dim=case.A)])}
-    buf = ReplayBuffer(make_scheme(case), groups, case.n_episodes, case.T + 1, preprocess=preprocess, device=device)
-    buf.load_arrays(case.data if data is None else data)
-    mac = mac_REGISTRY["basic_mac"](buf.scheme, groups, args)
-    logger = Logger(logging.getLogger("ma-test"))
-    learner = le_REGISTRY["actor_critic_learner"](mac, buf.scheme, logger, args)
-    if device != "cpu":
-        learner.cuda()
-    mac.agent.load_state_dict({k: th.from_numpy(v) for k, v in case.agent_params.items()})
-    cd = {k: th.from_numpy(v) for k, v in case.critic_params.items()}
-    learner.critic.load_state_dict(cd)
-    learner.target_critic.load_state_dict(cd)
-    return args, buf, mac, learner, logger
+    out = build_learner(case, make_a2c_args(case, **over), "actor_critic_learner", "ma-test", device, data=data)
+    load_actor_critic(case, out[2], out[3])
+    return out
 
 
 def learner_state(learner):

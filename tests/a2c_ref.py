@@ -3,9 +3,9 @@
 `a2c_ref_step(case, state, batch, dtype)` runs the whole step in float64 or in float32: the critic inputs (cv: state |
 last joint one-hot actions | agent id; ac: obs | agent id), V' of the target critic over every stored step, V of the
 critic over t < T, reward standardisation with running statistics, the n-step return as the specification's Python
-loops, the masked L2 critic loss, autograd, clip_grad_norm_ and a real torch.optim step; then the agent unroll (fc1 ->
-relu -> GRU cell -> fc2), the softmax policy (unavailable actions at -1e10 first under mask_before_softmax, no epsilon
-floor), pi = 1 on dead rows, the entropy, the policy-gradient loss, autograd, clip and a real torch.optim step. It
+loops, the masked L2 critic loss, autograd, clip_grad_norm_ and a real torch.optim step; then the agent unroll
+(tests/ref64.unroll on the one-hot of filled slots), the softmax policy (unavailable actions at -1e10 first under
+mask_before_softmax, no epsilon floor), pi = 1 on dead rows, the entropy, the policy-gradient loss, autograd, clip and a real torch.optim step. It
 shares no hand-derived backward with the kernels (pymarl_amd/csrc/a2c_kernels.hpp).
 
 The float32 run of the same function gives `e32`, each block's fp32 error against the float64 run from the same state;
@@ -120,7 +120,8 @@ class A2CCase:
         return OrderedDict((k, v[:, :max_t]) for k, v in self.data.items())
 
     def views(self):
-        return _View(self, self.agent_shapes, True), _View(self, self.critic_shapes, False)
+        return (ref64.FlatView(self, self.agent_shapes, True, self.obs_last_action),
+                ref64.FlatView(self, self.critic_shapes, False, self.obs_last_action))
 
     def init_state(self):
         """The learner's state before the first train(): flat float32 parameters, zero moments, step 0."""
@@ -129,25 +130,6 @@ class A2CCase:
         z = np.zeros_like
         return dict(agent=a, critic=c, target=c.copy(), a_m=z(a), a_v=z(a), c_m=z(c), c_v=z(c), step=0,
                     rew_ms=REW_MS_INIT)
-
-
-class _View:
-    """What ref64.grad_blocks / block_errors read of a case, over one flat parameter vector."""
-
-    def __init__(self, case, shapes, agent):
-        self.n, self.A, self.O = case.n, case.A, case.O
-        self.agent_shapes = shapes if agent else OrderedDict()
-        self.mixer_shapes = OrderedDict() if agent else shapes
-        self.obs_last_action, self.obs_agent_id = case.obs_last_action, True
-        self.mixer = "none"
-
-    def unflatten(self, flat):
-        out, o = OrderedDict(), 0
-        for k, s in list(self.agent_shapes.items()) + list(self.mixer_shapes.items()):
-            sz = int(np.prod(s))
-            out[k] = flat[o:o + sz].reshape(s)
-            o += sz
-        return out
 
 
 def blocks(case):
@@ -264,33 +246,6 @@ def logit_formula(p, avail, actions, m, adv, ec, mbs, M):
     return dl.masked_fill(avail == 0, 0.0) if mbs else dl
 
 
-def _unroll(p, obs, onehot, filled, flags, dt):
-    """BasicMAC.forward over t with RNNAgent: logits (B, T, n, A) and the fc1 pre-activations (B, T, n, H)."""
-    B, T, n, _ = obs.shape
-    A = onehot.shape[-1]
-    eye = th.eye(n, dtype=dt).expand(B, n, n)
-    h = th.zeros(B * n, H, dtype=dt)
-    outs, pres = [], []
-    for t in range(T):
-        parts = [obs[:, t]]
-        if flags[0]:
-            parts.append(th.zeros(B, n, A, dtype=dt) if t == 0 else onehot[:, t - 1] * filled[:, t - 1].unsqueeze(-1))
-        if flags[1]:
-            parts.append(eye)
-        x = th.cat(parts, -1).reshape(B * n, -1)
-        pre = x @ p["fc1.weight"].T + p["fc1.bias"]
-        pres.append(pre.reshape(B, n, H))
-        x1 = th.relu(pre)
-        gi = x1 @ p["rnn.weight_ih"].T + p["rnn.bias_ih"]
-        gh = h @ p["rnn.weight_hh"].T + p["rnn.bias_hh"]
-        r = th.sigmoid(gi[:, :H] + gh[:, :H])
-        z = th.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
-        c = th.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
-        h = (1.0 - z) * c + z * h
-        outs.append((h @ p["fc2.weight"].T + p["fc2.bias"]).reshape(B, n, A))
-    return th.stack(outs, 1), th.stack(pres, 1)
-
-
 def _params(view, flat, dt):
     return OrderedDict((k, th.nn.Parameter(th.tensor(np.asarray(v, np.float64), dtype=dt)))
                        for k, v in view.unflatten(np.asarray(flat)).items())
@@ -321,7 +276,7 @@ def _optim_step(case, view, P, clipped, m_flat, v_flat, step, dt):
             flat([opt.state[p]["exp_avg_sq" if adam else "square_avg"] for p in ps]))
 
 
-def _clip(P, max_norm):
+def _clip(P, max_norm):   # not ref64.clip: the float32 run's norm is accumulated in float64 here, by torch
     grads = OrderedDict((k, p.grad.detach().clone()) for k, p in P.items())
     norm = float(th.sqrt(sum((g.double() ** 2).sum() for g in grads.values())))
     coef = min(max_norm / (norm + 1e-6), 1.0)
@@ -378,8 +333,8 @@ def a2c_ref_step(case, state, batch, dtype=F64, Vt_override=None):
     cnorm, cclip = _clip(Pc, k["grad_norm_clip"])
     # 5. actor
     Pa = _params(av, state["agent"], dt)
-    logits, pre = _unroll(Pa, t(batch["obs"][:, :T]), t(batch["actions_onehot"][:, :T]), filled[:, :T],
-                          (case.obs_last_action, True), dt)
+    onehot = t(batch["actions_onehot"][:, :T]) * filled[:, :T, None]   # zero where the slot was never written
+    logits, pre, _ = ref64.unroll(Pa, t(batch["obs"][:, :T]), onehot, (case.obs_last_action, True), dt)
     logits.retain_grad()
     avail = th.tensor(np.asarray(batch["avail_actions"][:, :T]))
     actions = th.tensor(np.asarray(batch["actions"][:, :T], np.int64))

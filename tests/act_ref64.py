@@ -275,9 +275,9 @@ POLICY_A, POLICY_ROWS, POLICY_EPS = (1, 5, 64), (1, 3, 4, 5, 1023), (0.0, 0.3, 1
 # ------------------------------------------------------------------------------------------------------ the mixer
 def qmix(mp, agent_qs, states):
     """One-layer QMixer.forward on rows: agent_qs (rows, n), states (rows, S) -> q_tot (rows,) and the elu
-    pre-activations (rows, E). ref64._qmix, fed as a batch of one-step episodes."""
+    pre-activations (rows, E). ref64.qmix, fed as a batch of one-step episodes."""
     n = agent_qs.shape[1]
-    y, hw1, _, _ = ref64._qmix(mp, agent_qs.unsqueeze(1), states.unsqueeze(1), n)
+    y, hw1, _, _, _ = ref64.qmix(mp, agent_qs.unsqueeze(1), states.unsqueeze(1), n)
     Em = mp["hyper_w_final.weight"].shape[0]
     b1 = states @ mp["hyper_b_1.weight"].T + mp["hyper_b_1.bias"]
     pre = (agent_qs.unsqueeze(2) * hw1.abs().reshape(-1, n, Em)).sum(1) + b1

@@ -34,31 +34,12 @@ DELTA_CAP = 1e-3   # the critic update: a wrong sign, a dropped row or a missed 
 CRITIC_Q = ("cgrad_last", "csq", "cdelta")   # the critic-side quantities `judge` gates, then "agrad"
 
 
-class _View:
-    """What ref64.grad_blocks / block_errors read of a case, over one flat parameter vector of a COMA case."""
-
-    def __init__(self, case, shapes, agent):
-        self.n, self.A, self.O = case.n, case.A, case.O
-        self.agent_shapes = shapes if agent else OrderedDict()
-        self.mixer_shapes = OrderedDict() if agent else shapes
-        self.obs_last_action = self.obs_agent_id = True
-        self.mixer = "none"
-
-    def unflatten(self, flat):
-        out, o = OrderedDict(), 0
-        for k, s in list(self.agent_shapes.items()) + list(self.mixer_shapes.items()):
-            sz = int(np.prod(s))
-            out[k] = flat[o:o + sz].reshape(s)
-            o += sz
-        return out
-
-
 def agent_view(case):
-    return _View(case, case.agent_shapes, True)
+    return ref64.FlatView(case, case.agent_shapes, True, True)
 
 
 def critic_view(case):
-    return _View(case, case.critic_shapes, False)
+    return ref64.FlatView(case, case.critic_shapes, False, True)
 
 
 def coma_blocks(case):
@@ -74,7 +55,7 @@ def coma_blocks(case):
     return dict(critic=critic, agent=ref64.grad_blocks(agent_view(case)))
 
 
-def flat_of(named_arrays):
+def flat_of(named_arrays):   # of any {name: array}; ref64.flat_of is of a case's initial parameters
     return np.concatenate([np.asarray(v).ravel() for v in named_arrays.values()])
 
 
@@ -99,13 +80,7 @@ def _critic(cp, x):
     return z1, z2, th.relu(z2) @ cp["fc3.weight"].T + cp["fc3.bias"]
 
 
-def _clip(grads, max_norm):
-    norm = float(np.sqrt(sum(float((g * g).sum()) for g in grads.values())))
-    coef = min(max_norm / (norm + 1e-6), 1.0)
-    return norm, OrderedDict((k, g * coef) for k, g in grads.items())
-
-
-def _rmsprop(p, g, sq, lr, alpha, eps):
+def _rmsprop(p, g, sq, lr, alpha, eps):   # in place on {name: torch tensor}; ref64.rmsprop is on flat numpy vectors
     for k in p:
         sq[k] = alpha * sq[k] + (1.0 - alpha) * g[k] * g[k]
         p[k] = p[k] - lr * g[k] / (sq[k].sqrt() + eps)
@@ -185,7 +160,7 @@ def coma_ref64_step(case, agent, critic, target_critic, agent_sq, critic_sq, bat
         mtd = (q_taken - targets[:, t]) * mask_t
         loss = (mtd ** 2).sum() / msum
         loss.backward()
-        norm, g = _clip(OrderedDict((k, v.grad.clone()) for k, v in leaf.items()), clip)
+        norm, g = ref64.clip(OrderedDict((k, v.grad.clone()) for k, v in leaf.items()), clip, F64)
         live = (mask_t > 0).reshape(-1)
         kink1 = min(kink1, float(z1.detach()[live].abs().min()))
         kink2 = min(kink2, float(z2.detach()[live].abs().min()))
@@ -202,7 +177,7 @@ def coma_ref64_step(case, agent, critic, target_critic, agent_sq, critic_sq, bat
 
     # ---- the actor
     P = OrderedDict((k, _t64(v).requires_grad_(True)) for k, v in av.unflatten(np.asarray(agent)).items())
-    logits, pre = ref64._unroll(P, obs[:, :T], onehot[:, :T], (True, True))
+    logits, pre, _ = ref64.unroll(P, obs[:, :T], onehot[:, :T], (True, True), F64)
     pi = _policy(logits, avail, float(epsilon), bool(cfg.get("mask_before_softmax", True)))
     actions = actions_all[:, :-1]
     m = mask.expand(B, T, n)
@@ -212,7 +187,7 @@ def coma_ref64_step(case, agent, critic, target_critic, agent_sq, critic_sq, bat
     pi_taken = th.where(m == 0, th.ones_like(m), th.gather(pi, 3, actions).squeeze(3))
     coma_loss = -((adv * th.log(pi_taken)) * m).sum() / ms
     coma_loss.backward()
-    anorm, ag = _clip(OrderedDict((k, v.grad.clone()) for k, v in P.items()), clip)
+    anorm, ag = ref64.clip(OrderedDict((k, v.grad.clone()) for k, v in P.items()), clip, F64)
     ap = OrderedDict((k, v.detach().clone()) for k, v in P.items())
     asq = OrderedDict((k, _t64(v)) for k, v in av.unflatten(np.asarray(agent_sq)).items())
     _rmsprop(ap, ag, asq, cfg["lr"], alpha, eps)

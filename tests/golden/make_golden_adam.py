@@ -21,7 +21,7 @@ gradient at ANY step satisfied
     0 < |g| < NOISE_ROOM * tol(block) * max|ref64 block|
 
 where tol(block) is what tests/ref64.tolerances grants the element's gradient block (its finest block of
-ref64.grad_blocks) from the reference's own fp32 error against tests/ref64.ref64_step at the same state with the same
+ref64.grad_blocks) from the reference's own fp32 error against tests/ref64.ref_step at the same state with the same
 double-Q decisions. tests/test_gpu_adam.py bounds those elements by Adam's worst-case step and every other one
 tightly. The mask may cover at most MASK_MAX of the parameters: asserted here (change `data_seed` below if TINY's
 seeds ever exceed it), with the share printed and stored.
@@ -79,7 +79,7 @@ def noise_mask(case):
     for k, seen in enumerate(SEEN):
         nb, _ = case.batch(k)
         acts = case.z["cur_max_actions"][k][:, :nb["obs"].shape[1] - 1].astype(np.int64)
-        r = ref64.ref64_step(case, seen["params"], seen["targets"], nb, cur_max_override=acts)
+        r = ref64.ref_step(case, seen["params"], seen["targets"], nb, cur_max_override=acts)
         e32 = ref64.block_errors(seen["grads"], r.clipped, case)
         tol = ref64.tolerances(e32)
         thr = {n_: np.zeros(r.clipped[n_].shape) for n_ in names}

@@ -4,7 +4,6 @@ from __future__ import annotations
 import logging
 from types import SimpleNamespace as SN
 
-import numpy as np
 import torch as th
 
 from pymarl_amd.components.episode_buffer import ReplayBuffer
@@ -12,6 +11,7 @@ from pymarl_amd.components.transforms import OneHot
 from pymarl_amd.controllers import REGISTRY as mac_REGISTRY
 from pymarl_amd.learners import REGISTRY as le_REGISTRY
 from pymarl_amd.utils.logging import Logger
+from tests.golden_utils import rel_err as rel  # noqa: F401  (the tests' name for it)
 
 
 CKPT = {name: "ckpt_{}_step2".format(name) for name in ("tiny_qmix", "tiny_vdn")}
@@ -41,20 +41,35 @@ def make_scheme(case):
     }
 
 
-def build(case, device="cuda", buffer_device=None, **over):
-    """buffer_device: where the ReplayBuffer lives (default: with the learner); "cpu" is the reference's
-    buffer_cpu_only layout (run.py:137-139)."""
-    args = make_args(case, **over)
+def build_learner(case, args, learner, log, device="cuda", buffer_device=None, data=None):
+    """What the three builders share: the replay (one-hot preprocess, `data` or the case's arrays) on buffer_device
+    (default: with the learner), the MAC, the logger and the `learner` of le_REGISTRY, moved to `device`."""
     groups = {"agents": case.n}
     preprocess = {"actions": ("actions_onehot", [OneHot(out_dim=case.A)])}
     buf = ReplayBuffer(make_scheme(case), groups, case.n_episodes, case.T + 1, preprocess=preprocess,
                        device=buffer_device or device)
-    buf.load_arrays(case.data)
+    buf.load_arrays(case.data if data is None else data)
     mac = mac_REGISTRY["basic_mac"](buf.scheme, groups, args)
-    logger = Logger(logging.getLogger("mq-test"))
-    learner = le_REGISTRY["q_learner"](mac, buf.scheme, logger, args)
+    logger = Logger(logging.getLogger(log))
+    learner = le_REGISTRY[learner](mac, buf.scheme, logger, args)
     if device != "cpu":
         learner.cuda()
+    return args, buf, mac, learner, logger
+
+
+def load_actor_critic(case, mac, learner):
+    """The case's agent and critic weights into the MAC, the critic and the target critic."""
+    mac.agent.load_state_dict({k: th.from_numpy(v) for k, v in case.agent_params.items()})
+    cd = {k: th.from_numpy(v) for k, v in case.critic_params.items()}
+    learner.critic.load_state_dict(cd)
+    learner.target_critic.load_state_dict(cd)
+
+
+def build(case, device="cuda", buffer_device=None, **over):
+    """buffer_device: where the ReplayBuffer lives (default: with the learner); "cpu" is the reference's
+    buffer_cpu_only layout (run.py:137-139)."""
+    out = build_learner(case, make_args(case, **over), "q_learner", "mq-test", device, buffer_device)
+    mac, learner = out[2], out[3]
     sd = {k: th.from_numpy(v) for k, v in case.agent_params.items()}
     mac.agent.load_state_dict(sd)
     learner.target_mac.agent.load_state_dict(sd)
@@ -62,7 +77,7 @@ def build(case, device="cuda", buffer_device=None, **over):
         md = {k: th.from_numpy(v) for k, v in case.mixer_params.items()}
         learner.mixer.load_state_dict(md)
         learner.target_mixer.load_state_dict(md)
-    return args, buf, mac, learner, logger
+    return out
 
 
 def flat_params(learner):
@@ -75,12 +90,6 @@ def flat_targets(learner):
 
 def flat_grads(learner):
     return learner._grad[:learner.n_params].detach().cpu().numpy().copy()
-
-
-def rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(1e-30, np.abs(b).max()))
 
 
 def make_coma_args(case, **over):
@@ -97,20 +106,9 @@ def make_coma_args(case, **over):
 
 
 def build_coma(case, device="cuda", **over):
-    args = make_coma_args(case, **over)
-    groups = {"agents": case.n}
-    preprocess = {"actions": ("actions_onehot", [OneHot(out_dim=case.A)])}
-    buf = ReplayBuffer(make_scheme(case), groups, case.n_episodes, case.T + 1, preprocess=preprocess, device=device)
-    buf.load_arrays(case.data)
-    mac = mac_REGISTRY["basic_mac"](buf.scheme, groups, args)
-    logger = Logger(logging.getLogger("mc-test"))
-    learner = le_REGISTRY["coma_learner"](mac, buf.scheme, logger, args)
-    learner.cuda()
-    mac.agent.load_state_dict({k: th.from_numpy(v) for k, v in case.agent_params.items()})
-    cd = {k: th.from_numpy(v) for k, v in case.critic_params.items()}
-    learner.critic.load_state_dict(cd)
-    learner.target_critic.load_state_dict(cd)
-    return args, buf, mac, learner, logger
+    out = build_learner(case, make_coma_args(case, **over), "coma_learner", "mc-test", device)
+    load_actor_critic(case, out[2], out[3])
+    return out
 
 
 # The library's two switch variables (pymarl_amd/csrc/switches.hpp): MQ_PLAN for plan overrides, MQ_DIAG for

@@ -1,6 +1,6 @@
 """tests/act_ref64.py pinned on the CPU: every float64 reference of the acting path against torch's own float64
 nn.Linear / nn.GRUCell / softmax / elu / max(dim), assembled separately (act_ref64.ModAgent / ModMixer / policy_mod,
-ref64._unroll, the reference's masked max), so that a typo in a reference cannot become the standard; and the inputs
+ref64.unroll, the reference's masked max), so that a typo in a reference cannot become the standard; and the inputs
 of tests/test_gpu_acting.py hold what its rows are there for."""
 import copy
 
@@ -77,7 +77,7 @@ def test_mac_case_has_the_episodes_it_is_there_for():
 @pytest.mark.parametrize("n", [3, 2])
 def test_mac_chain_is_ref64_unroll_and_the_reference_builder(flags, n):
     """build_inputs (raw actions / filled) against the reference's recipe on the preprocessed actions_onehot, the chain
-    against ref64._unroll and against torch's modules."""
+    against ref64.unroll and against torch's modules."""
     case = R.mac_case(flags, n)
     d, Tp = case.data, R.MAC["T"] + 1
     for t in range(Tp):
@@ -93,7 +93,8 @@ def test_mac_chain_is_ref64_unroll_and_the_reference_builder(flags, n):
     p = R.named64(case.agent_params)
     q, h = R.mac_chain(p, d, case.A, flags, Tp)
     assert q.shape == (Tp, 6 * n, case.A) and h.shape == (Tp, 6 * n, R.H)
-    Q, pre = ref64._unroll(p, th.as_tensor(d["obs"], dtype=F64), th.as_tensor(d["actions_onehot"], dtype=F64), flags)
+    Q, pre, _ = ref64.unroll(p, th.as_tensor(d["obs"], dtype=F64), th.as_tensor(d["actions_onehot"], dtype=F64), flags,
+                              F64)
     assert close(q, Q.permute(1, 0, 2, 3).reshape(Tp, 6 * n, case.A))
     assert (pre > 0).any() and (pre < 0).any()
     mod = R.ModAgent(case.I, case.A).double()
@@ -199,10 +200,10 @@ def test_qmix_is_torchs_modules(n, S, E, rows):
 
 
 def test_ref64_qmix_keeps_its_learner_shape():
-    """ref64._qmix now reads the embed dim from the parameters: the learner cases' E = 32 is unchanged."""
+    """ref64.qmix now reads the embed dim from the parameters: the learner cases' E = 32 is unchanged."""
     mod, qs, st = R.mixer_case(3, 48, ref64.E, 8)
     mp = R.named64({k: v.detach().numpy() for k, v in mod.state_dict().items()})
-    y, hw1, hwf, hv = ref64._qmix(mp, qs.double().reshape(2, 4, 3), st.double().reshape(2, 4, 48), 3)
+    y, hw1, hwf, hv, _ = ref64.qmix(mp, qs.double().reshape(2, 4, 3), st.double().reshape(2, 4, 48), 3)
     assert y.shape == (2, 4, 1) and hw1.shape == (8, 3 * ref64.E) and hwf.shape == hv.shape == (8, ref64.E)
 
 

@@ -135,7 +135,7 @@ def test_restated_module_agrees_with_ref_steps_unroll():
     th.manual_seed(4)
     m = R.RefFFAgent(9, 4).double()
     obs = th.randn(2, 3, 1, 9, dtype=th.float64)
-    q, pre, pre2 = R._unroll(dict(m.state_dict()), obs, th.zeros(2, 3, 1, 4, dtype=th.float64), (False, False),
+    q, pre, pre2 = ref64.unroll(dict(m.state_dict()), obs, th.zeros(2, 3, 1, 4, dtype=th.float64), (False, False),
                              th.float64)
     qm, hm = m(obs.reshape(-1, 9), th.full((6, 64), float("nan"), dtype=th.float64))   # the hidden state is ignored
     assert th.allclose(q.reshape(-1, 4), qm, rtol=1e-13, atol=1e-13)
@@ -264,14 +264,14 @@ def steps():
     for row in R.ROW_SHAPES:
         for mixer in MIXERS_OF.get(row, ("qmix",)):
             case = R.synth_case(row, mixer)
-            p = t = R.flat_of(case)
+            p = t = ref64.flat_of(case)
             sq = np.zeros_like(p, np.float64)
             recs = []
             for k in range(2):
                 nb, _ = case.batch(k)
-                r = R.ref_step(case, p, t, nb)
+                r = ref64.ref_step(case, p, t, nb)
                 recs.append((case, p, t, nb, r))
-                p, sq = R.rmsprop(case, p, sq, r.clipped_flat)
+                p, sq = ref64.rmsprop(case, p, sq, r.clipped_flat)
                 p = p.astype(np.float32)
             out[row, mixer] = recs
     return out
@@ -293,14 +293,14 @@ def test_reference_is_finite_and_clear_of_the_kinks(steps, row):
 def test_flag_rows_are_finite_and_clear_of_the_kinks(flags):
     case = R.synth_case("part", flags=flags)
     assert case.I == 30 + (9 if flags[0] else 0) + (3 if flags[1] else 0)
-    p = R.flat_of(case)
+    p = ref64.flat_of(case)
     nb, _ = case.batch(0)
-    r = R.ref_step(case, p, p, nb)
+    r = ref64.ref_step(case, p, p, nb)
     assert np.isfinite(r.clipped_flat).all()
     ref64.assert_clear_of_kinks(r, "part flags {}".format(flags))
-    assert set(R.grad_blocks(case)) >= {"fc1.weight[obs]"}
-    assert ("fc1.weight[last_action]" in R.grad_blocks(case)) == flags[0]
-    assert ("fc1.weight[agent_id]" in R.grad_blocks(case)) == flags[1]
+    assert set(ref64.grad_blocks(case)) >= {"fc1.weight[obs]"}
+    assert ("fc1.weight[last_action]" in ref64.grad_blocks(case)) == flags[0]
+    assert ("fc1.weight[agent_id]" in ref64.grad_blocks(case)) == flags[1]
 
 
 def test_ragged_row_has_padded_steps_and_unfilled_previous_slots(steps):
@@ -317,9 +317,9 @@ def test_ragged_row_has_padded_steps_and_unfilled_previous_slots(steps):
 def test_float32_reference_leaves_the_gate_room(steps):
     """e32 of every block on `part` is below TOL_CAP / TOL_ROOM: the cap never decides a block there."""
     case, p, t, nb, r64 = steps["part", "qmix"][0]
-    r32 = R.ref_step(case, p, t, nb, dtype=th.float32, cur_max_override=r64.cur_max_actions,
+    r32 = ref64.ref_step(case, p, t, nb, dtype=th.float32, cur_max_override=r64.cur_max_actions,
                      relu_override=r64.pre > 0, hid_relu_override=r64.pre2 > 0)
-    e32 = R.block_errors(r32.clipped_flat, r64.clipped, case)
+    e32 = ref64.block_errors(r32.clipped_flat, r64.clipped, case)
     assert set(R.ff_agent_shapes(case.I, case.A)) <= set(e32)
     worst = max(e32, key=e32.get)
     print("worst e32 {:.3g} at {}".format(e32[worst], worst))
@@ -329,15 +329,15 @@ def test_float32_reference_leaves_the_gate_room(steps):
 
 def test_overrides_at_the_references_own_decisions_change_nothing(steps):
     case, p, t, nb, r = steps["tiles", "qmix"][0]
-    r2 = R.ref_step(case, p, t, nb, cur_max_override=r.cur_max_actions, relu_override=r.pre > 0,
+    r2 = ref64.ref_step(case, p, t, nb, cur_max_override=r.cur_max_actions, relu_override=r.pre > 0,
                     hid_relu_override=r.pre2 > 0)
     assert np.array_equal(r2.clipped_flat, r.clipped_flat)
-    c = R.classify(r, r.cur_max_actions, r.pre > 0, r.pre2 > 0)
+    c = ref64.classify(r, r.cur_max_actions, r.pre > 0, r.pre2 > 0)
     assert c["dq_flips"] == c["relu_flips"] == c["hid_relu_flips"] == 0
     assert c["hid_relu_decisions"] == r.pre2.size
     flipped = r.pre2 > 0
     flipped[0, 0, 0, 0] = not flipped[0, 0, 0, 0]   # and a flipped decision is counted
-    assert R.classify(r, r.cur_max_actions, r.pre > 0, flipped)["hid_relu_flips"] == 1
+    assert ref64.classify(r, r.cur_max_actions, r.pre > 0, flipped)["hid_relu_flips"] == 1
 
 
 def test_ffn_reference_differs_from_the_gru_reference(steps):
@@ -347,6 +347,6 @@ def test_ffn_reference_differs_from_the_gru_reference(steps):
     d = R.ROW_SHAPES["part"]["dims"]
     gcase = SynthCase("gru_part", n_episodes=d["B"], steps=2, mixer="qmix", ragged=False, min_len=1, **d)
     gp = np.concatenate([v.ravel() for v in list(gcase.agent_params.values()) + list(gcase.mixer_params.values())])
-    rg = ref64.ref64_step(gcase, gp, gp, gcase.batch(0)[0])
+    rg = ref64.ref_step(gcase, gp, gp, gcase.batch(0)[0])
     assert abs(rg.loss - r.loss) > 1e-3 * abs(r.loss)
     assert gp.size != p.size

@@ -17,6 +17,7 @@ import torch as th
 
 from tests import coma_ref64, ref64
 from tests.golden_utils import COMA_STATS, ComaCase
+from tests.golden_utils import rel_err as rel
 from tests.gpu_helpers import set_switch
 
 pytestmark = pytest.mark.gpu
@@ -31,12 +32,6 @@ def get(cases, name):
     if name not in cases:
         cases[name] = ComaCase(name)
     return cases[name]
-
-
-def rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(1e-30, np.abs(b).max()))
 
 
 def load_state(learner, o):

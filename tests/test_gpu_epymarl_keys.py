@@ -344,7 +344,7 @@ def test_standardised_tails_grad_blocks_vs_ref64(synth_cases, row, monkeypatch):
         r, got, on_gpu = P.classify_decisions(learner, o, nb, fw)
         assert r["dq_flips_outside_ties"] == 0, (row, k, r)
         assert r["relu_flips_outside_ties"] == 0, (row, k, r)
-        ref = ref64.ref64_step(case, params, targets, nb, cur_max_override=got, relu_override=on_gpu)
+        ref = ref64.ref_step(case, params, targets, nb, cur_max_override=got, relu_override=on_gpu)
         if mixer == "qmix":
             ref64.assert_clear_of_kinks(ref, "{} step {}".format(row, k))
         e32 = ref64.block_errors(oracle_clipped(o, nb, got, on_gpu), ref.clipped, case)

@@ -1,4 +1,4 @@
-"""The feed-forward agent (use_rnn: False, epymarl's key) on the GPU, against tests/ffn_ref.py.
+"""The feed-forward agent (use_rnn: False, epymarl's key) on the GPU, against tests/ref64.py on ffn_ref.py's cases.
 
 * Every gradient block of two train() steps against the float64 reference, by tests/test_gpu_hyper2.py's procedure and
   ref64's tolerance rule with e32 from the reference's float32 run: step 1 starts from the GPU's own parameters; the
@@ -120,22 +120,22 @@ def test_grad_blocks_vs_ref64(cases, row, monkeypatch):
         assert np.isfinite(g_gpu).all(), (row, k)
         dec = decisions(learner, case)
         assert dec[2].shape == (case.B, nb["obs"].shape[1], case.n, 64)
-        own = R.ref_step(case, params, targets, nb)   # the reference's own decisions at this state
-        r = R.classify(own, dec[0], dec[1], dec[2])
+        own = ref64.ref_step(case, params, targets, nb)   # the reference's own decisions at this state
+        r = ref64.classify(own, dec[0], dec[1], dec[2])
         assert r["dq_flips_outside_ties"] == 0, (row, k, r)
         assert r["relu_flips_outside_ties"] == 0, (row, k, r)
         assert r["hid_relu_flips_outside_ties"] == 0, (row, k, r)
         over = dict(cur_max_override=dec[0], relu_override=dec[1], hid_relu_override=dec[2])
         if case.He:
-            hyp_tie = np.abs(own.a1) <= R.RELU_EPS
+            hyp_tie = np.abs(own.a1) <= ref64.RELU_EPS
             assert int(((dec[3] != (own.a1 > 0)) & ~hyp_tie).sum()) == 0, (row, k)
             over["hyp_relu_override"] = dec[3]
-        ref = R.ref_step(case, params, targets, nb, **over)
+        ref = ref64.ref_step(case, params, targets, nb, **over)
         if case.mixer == "qmix":
             ref64.assert_clear_of_kinks(ref, "{} step {}".format(row, k))
-        e32 = R.block_errors(R.ref_step(case, params, targets, nb, dtype=th.float32, **over).clipped_flat, ref.clipped,
-                             case)
-        errs = R.block_errors(g_gpu, ref.clipped, case)
+        e32 = ref64.block_errors(ref64.ref_step(case, params, targets, nb, dtype=th.float32, **over).clipped_flat,
+                                 ref.clipped, case)
+        errs = ref64.block_errors(g_gpu, ref.clipped, case)
         tol = ref64.tolerances(e32)
         ratio = ref64.ratios(errs, e32)
         worst = max(ratio, key=ratio.get)
@@ -179,8 +179,8 @@ def test_forward_vs_ref64(cases, row):
     p = flat_params(learner)
     learner.train(batch, 0, case.episodes[0])
     check_path(learner, case)
-    r64 = R.ref_step(case, p, p, nb)
-    r32 = R.ref_step(case, p, p, nb, dtype=th.float32)
+    r64 = ref64.ref_step(case, p, p, nb)
+    r32 = ref64.ref_step(case, p, p, nb, dtype=th.float32)
     bad, rec = [], {}
     for which, name in ((0, "mac_out"), (1, "target_mac_out_full"), (3, "x1"), (9, "hid")):
         got = learner.last_intermediate(which).cpu().numpy()
@@ -287,7 +287,7 @@ def test_mac_forward_per_step_and_greedy_actions_are_the_learners(cases):
         act = greedy_actions(qt, avail).cpu().numpy()
         masked = np.where(nb["avail_actions"][:, t + 1] == 0, -9999999.0, mo[:, t + 1].astype(np.float64))
         top2 = -np.sort(-masked, axis=2)[..., :2]
-        clear = (top2[..., 0] - top2[..., 1]) > R.MARGIN_EPS * np.maximum(1.0, np.abs(top2[..., 0]))
+        clear = (top2[..., 0] - top2[..., 1]) > ref64.MARGIN_EPS * np.maximum(1.0, np.abs(top2[..., 0]))
         clear &= nb["avail_actions"][:, t + 1].sum(-1) > 0
         assert (act[clear] == cur[:, t][clear]).all(), t
         checked += int(clear.sum())
@@ -503,7 +503,7 @@ def test_two_rank_dp_equals_single_process(cases, tmp_path):
     for k in range(DP_STEPS):
         assert rel(dp["stats"][k], ref["stats"][k]) < 1e-3, (k, dp["stats"][k], ref["stats"][k])
     g0 = dp["grads"][0].astype(np.float64)
-    assert rel(dp["params"][0], R.flat_of(case) - 5e-4 * g0 / (np.sqrt(0.01 * g0 * g0) + 1e-5)) < 1e-6
+    assert rel(dp["params"][0], ref64.flat_of(case) - 5e-4 * g0 / (np.sqrt(0.01 * g0 * g0) + 1e-5)) < 1e-6
     assert np.abs(dp["params"][-1] - ref["params"][-1]).max() <= 20 * 5e-4
 
 

@@ -1,4 +1,4 @@
-"""The two-layer QMIX hypernetwork (hypernet_layers: 2) on the GPU, against tests/hyper2_ref.py.
+"""The two-layer QMIX hypernetwork (hypernet_layers: 2) on the GPU, against tests/ref64.py on hyper2_ref.py's cases.
 
 * QMixer.forward (mq_qmix_forward2) against the restated upstream module in float64: the GPU's error is at most
   16 * max(error of the same module in fp32 on the CPU, 2e-7 * max|ref|).
@@ -122,17 +122,17 @@ def test_grad_blocks_vs_ref64(cases, row, monkeypatch):
         assert plan["hyper_layers"] == 2, plan
         got, on_gpu, hyp_on = decisions(learner)
         assert hyp_on.shape == (case.B, nb["obs"].shape[1] - 1, 2 * case.He)
-        own = R.ref_step(case, params, targets, nb)   # the reference's own decisions at this state
-        r = R.classify(own, got, on_gpu, hyp_on)
+        own = ref64.ref_step(case, params, targets, nb)   # the reference's own decisions at this state
+        r = ref64.classify(own, got, on_gpu, got_hyp_relu=hyp_on)
         assert r["dq_flips_outside_ties"] == 0, (row, k, r)
         assert r["relu_flips_outside_ties"] == 0, (row, k, r)
         assert r["hyp_relu_flips_outside_ties"] == 0, (row, k, r)
         over = dict(cur_max_override=got, relu_override=on_gpu, hyp_relu_override=hyp_on)
-        ref = R.ref_step(case, params, targets, nb, **over)
+        ref = ref64.ref_step(case, params, targets, nb, **over)
         ref64.assert_clear_of_kinks(ref, "{} step {}".format(row, k))
-        e32 = R.block_errors(R.ref_step(case, params, targets, nb, dtype=th.float32, **over).clipped_flat, ref.clipped,
-                             case)
-        errs = R.block_errors(g_gpu, ref.clipped, case)
+        e32 = ref64.block_errors(ref64.ref_step(case, params, targets, nb, dtype=th.float32, **over).clipped_flat,
+                                 ref.clipped, case)
+        errs = ref64.block_errors(g_gpu, ref.clipped, case)
         tol = ref64.tolerances(e32)
         ratio = ref64.ratios(errs, e32)
         worst = max(ratio, key=ratio.get)
@@ -168,7 +168,7 @@ def run_steps(case, steps, **over):
 
 def test_optimiser_and_target_update_reach_the_new_tensors(cases):
     case = get_case(cases, "base")
-    p0 = case.unflatten(R.flat_of(case))
+    p0 = case.unflatten(ref64.flat_of(case))
     buf, learner = run_steps(case, 1)
     p1, t1 = case.unflatten(flat_params(learner)), case.unflatten(flat_targets(learner))
     g = case.unflatten(flat_grads(learner))
@@ -323,7 +323,7 @@ def test_two_rank_dp_equals_single_process(cases, tmp_path):
     for k in range(DP_STEPS):
         assert rel(dp["stats"][k], ref["stats"][k]) < 1e-3, (k, dp["stats"][k], ref["stats"][k])
     g0 = dp["grads"][0].astype(np.float64)
-    assert rel(dp["params"][0], R.flat_of(case) - 5e-4 * g0 / (np.sqrt(0.01 * g0 * g0) + 1e-5)) < 1e-6
+    assert rel(dp["params"][0], ref64.flat_of(case) - 5e-4 * g0 / (np.sqrt(0.01 * g0 * g0) + 1e-5)) < 1e-6
     assert np.abs(dp["params"][-1] - ref["params"][-1]).max() <= 20 * 5e-4
 
 

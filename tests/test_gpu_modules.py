@@ -7,13 +7,9 @@ import pytest
 import torch as th
 
 from tests.golden_utils import Case, ComaCase
+from tests.golden_utils import rel_err as rel
 
 pytestmark = pytest.mark.gpu
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(1e-30, np.abs(b).max()))
 
 
 def test_qmixer_forward_vs_reference():

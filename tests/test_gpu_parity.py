@@ -30,12 +30,11 @@ import torch as th
 
 from tests.golden_utils import Case
 from tests.gpu_helpers import set_switch
+from tests.ref64 import MARGIN_EPS, RELU_EPS, near_ties
 
 pytestmark = pytest.mark.gpu
 
 STATS = ["loss", "grad_norm", "td_error_abs", "q_taken_mean", "target_mean"]
-MARGIN_EPS = 1e-5   # argmax-equal wherever the top-2 gap exceeds 1e-5 * max(1, |Q|)
-RELU_EPS = 1e-5
 HOLD_STEPS = 12     # the oracle itself holds the reference's cfg2 loss trajectory to 1e-4 for 12 steps
 LOSS_RTOL = 1e-4    # north_star: "loss trajectory to 1e-4 rel on a fixed seed"
 
@@ -68,12 +67,9 @@ def classify_decisions(learner, o, nb, fw):
         q = q[:, 1:]
     else:                             # target_mac_out.max(dim=3) (q_learner.py:77-78), masked at :68
         q = fw["target_mac_out"]
-    top2 = -np.sort(-q, axis=3)[..., :2]
-    margin = top2[..., 0] - top2[..., 1]
-    tie = margin <= MARGIN_EPS * np.maximum(1.0, np.abs(top2[..., 0]))
     # live transitions (q_learner.py:39-44 mask): padded slots (every action masked) are ties by construction but
     # never reach the loss, so they are counted separately
-    live = np.broadcast_to(fw["mask"] > 0, tie.shape)
+    tie, live = near_ties(q, fw["mask"])
     got = learner.last_cur_max_actions().cpu().numpy()
     dq_flip = got != fw["cur_max_actions"]
     on_gpu = learner.last_intermediate(3).cpu().numpy() > 0

@@ -11,11 +11,12 @@ import numpy as np
 import pytest
 import torch as th
 
+from tests.ref64 import MARGIN_EPS
+
 pytestmark = pytest.mark.gpu
 
 # BASELINE configs[0]'s shape (SMAC 3m, upstream obs / state sizes): episode_limit 60
 N, A, O, S, LIMIT = 3, 9, 30, 48, 60
-MARGIN_EPS = 1e-5   # argmax-equal wherever the top-2 gap exceeds 1e-5 * max(1, |Q|)
 
 
 def build(kind="episode", bsr=1, cpu_only=False):

@@ -125,14 +125,14 @@ def steps():
     out = {}
     for row in R.ROW_SHAPES:
         case = R.synth_case2(row)
-        p = t = R.flat_of(case)
+        p = t = ref64.flat_of(case)
         sq = np.zeros_like(p, np.float64)
         recs = []
         for k in range(2):
             nb, _ = case.batch(k)
-            r = R.ref_step(case, p, t, nb)
+            r = ref64.ref_step(case, p, t, nb)
             recs.append((case, p, t, nb, r))
-            p, sq = R.rmsprop(case, p, sq, r.clipped_flat)
+            p, sq = ref64.rmsprop(case, p, sq, r.clipped_flat)
             p = p.astype(np.float32)
         out[row] = recs
     return out
@@ -150,9 +150,9 @@ def test_float32_reference_leaves_the_gate_room(steps):
     """e32 of every block on the base shape is below TOL_CAP / TOL_ROOM: the cap never decides a block there, so
     tol = TOL_ROOM * max(e32, E32_FLOOR) is a bound an fp32 implementation with another summation order can meet."""
     case, p, t, nb, r64 = steps["base"][0]
-    r32 = R.ref_step(case, p, t, nb, dtype=th.float32, cur_max_override=r64.cur_max_actions,
+    r32 = ref64.ref_step(case, p, t, nb, dtype=th.float32, cur_max_override=r64.cur_max_actions,
                      relu_override=r64.pre > 0, hyp_relu_override=r64.a1 > 0)
-    e32 = R.block_errors(r32.clipped_flat, r64.clipped, case)
+    e32 = ref64.block_errors(r32.clipped_flat, r64.clipped, case)
     assert set(R.mixer2_shapes(case.S, case.n, case.He)) <= set(e32)
     worst = max(e32, key=e32.get)
     print("worst e32 {:.3g} at {}".format(e32[worst], worst))
@@ -162,10 +162,10 @@ def test_float32_reference_leaves_the_gate_room(steps):
 
 def test_overrides_at_the_references_own_decisions_change_nothing(steps):
     case, p, t, nb, r = steps["base_he20"][0]
-    r2 = R.ref_step(case, p, t, nb, cur_max_override=r.cur_max_actions, relu_override=r.pre > 0,
+    r2 = ref64.ref_step(case, p, t, nb, cur_max_override=r.cur_max_actions, relu_override=r.pre > 0,
                     hyp_relu_override=r.a1 > 0)
     assert np.array_equal(r2.clipped_flat, r.clipped_flat)
-    c = R.classify(r, r.cur_max_actions, r.pre > 0, r.a1 > 0)
+    c = ref64.classify(r, r.cur_max_actions, r.pre > 0, got_hyp_relu=r.a1 > 0)
     assert c["dq_flips"] == c["relu_flips"] == c["hyp_relu_flips"] == 0
     assert c["hyp_relu_decisions"] == r.a1.size
 
@@ -175,7 +175,7 @@ def test_restated_module_agrees_with_ref_step_mixer():
     th.manual_seed(3)
     m = R.RefQMixer2(3, 48, 32, 20).double()
     qs, st = th.randn(2, 5, 3, dtype=th.float64), th.randn(2, 5, 48, dtype=th.float64)
-    y = R._qmix2(dict(m.state_dict()), qs, st, 3)[0]
+    y = ref64.qmix(dict(m.state_dict()), qs, st, 3)[0]
     assert th.allclose(m(qs, st), y, rtol=1e-13, atol=1e-13)
 
 
@@ -186,14 +186,14 @@ def test_reference_restatement_reproduces_the_reference_learners_golden_step():
     z = case.z
     nb, ids = case.batch(0)
     assert np.array_equal(ids, z["ids"][0])
-    p = R.flat_of(case)
-    r = R.ref_step(case, p, p, nb)
+    p = ref64.flat_of(case)
+    r = ref64.ref_step(case, p, p, nb)
     assert abs(r.loss - float(z["stat_loss"][0])) <= 1e-6 * r.loss
     for k in ("grad_norm", "td_error_abs", "q_taken_mean", "target_mean"):
         assert abs(r.stats[k] - float(z["stat_" + k][0])) <= 2e-6 * abs(r.stats[k]), k
     assert np.array_equal(r.cur_max_actions, z["step0_cur_max_actions"])
     assert np.abs(r.clipped_flat - z["step0_grads_clipped"]).max() <= 1e-5 * np.abs(r.clipped_flat).max()
-    p1, _ = R.rmsprop(case, p, np.zeros_like(p, np.float64), z["step0_grads_clipped"])
+    p1, _ = ref64.rmsprop(case, p, np.zeros_like(p, np.float64), z["step0_grads_clipped"])
     assert np.abs(p1 - z["step_params"][0]).max() <= 1e-6
 
 

@@ -47,7 +47,7 @@ def check_against_oracle(case, over_fn=None):
     o, _, fw0, _ = oracle_raw(case, nb)
     over = over_fn(case, nb, fw0) if over_fn else {}
     o, flat, fw, g = oracle_raw(case, nb, **over)
-    r = ref64.ref64_step(case, o.flat("params"), o.flat("targets"), nb, **over)
+    r = ref64.ref_step(case, o.flat("params"), o.flat("targets"), nb, **over)
     errs = ref64.block_errors(flat, r.grads, case)
     print(case.name, "worst block", max(errs, key=errs.get), max(errs.values()))
     for k, e in errs.items():
@@ -194,7 +194,7 @@ def base_gradients(synth):
     c = synth("base")
     nb, _ = c.batch(0)
     o, flat, fw, _ = oracle_raw(c, nb)
-    r = ref64.ref64_step(c, o.flat("params"), o.flat("targets"), nb)
+    r = ref64.ref_step(c, o.flat("params"), o.flat("targets"), nb)
     e32 = ref64.block_errors(flat, r.grads, c)
     return c, nb["obs"].shape[1] - 1, flat, r, e32
 
@@ -224,7 +224,7 @@ def test_kink_preconditions(synth, shape):
     c = synth(shape)
     nb, _ = c.batch(0)
     o = OracleQLearner(c.agent_params, c.mixer_params, c.cfg())
-    r = ref64.ref64_step(c, o.flat("params"), o.flat("targets"), nb)
+    r = ref64.ref_step(c, o.flat("params"), o.flat("targets"), nb)
     print(shape, ref64.kink_minima(r))
     ref64.assert_clear_of_kinks(r, c.name)
     assert (r.mask > 0).sum() < r.mask.size   # ragged: dead rows exist and are left out of the minima
