@@ -54,6 +54,18 @@ typedef struct ma_adam {
   float beta1, beta2, eps, weight_decay;
 } ma_adam;
 
+/* PPO (epymarl's ppo_learner) in the one-step actor-critic's place: ma_train_step runs `epochs`
+ * optimisation epochs over the batch, each one critic step and one actor step on the clipped surrogate
+ * min(ratio adv, clamp(ratio, lo, hi) adv), ratio = exp(log pi_u - old), old = epoch 0's own log pi_u,
+ * lo = (float)(1.0 - (double)eps_clip), hi = (float)(1.0 + (double)eps_clip). The returns, the standardised rewards
+ * and the running reward statistics are formed once per step. epoch_stats: DEVICE memory [epochs][MA_NSTATS], row k
+ * = stats as epoch k's applies left it, with the number of live rows whose surrogate gradient was cut at [15]. */
+typedef struct ma_ppo {
+  int32_t epochs;       /* >= 1 */
+  float eps_clip;       /* 0 < eps_clip < 1 */
+  float* epoch_stats;
+} ma_ppo;
+
 /* What the last ma_train_step launched (host tests read the edges off it). */
 typedef struct ma_plan {
   int32_t rows;           /* T * B * n: the online critic's and the actor's rows */
@@ -74,6 +86,8 @@ typedef struct ma_plan {
   int32_t bwd_blocks;     /* the BPTT's workgroups */
   int32_t reward_norm;    /* 1: the step standardised its rewards */
   int32_t adam;           /* 1: Adam applied, 0: RMSprop */
+  int32_t epochs;         /* optimisation epochs the step ran: 1, or ma_ppo.epochs */
+  int32_t hoisted;        /* PPO: launches and copies made once per step, not once per epoch (0: not a PPO step) */
 } ma_plan;
 
 typedef struct ma_handle ma_handle;
@@ -89,9 +103,13 @@ int ma_bind(ma_handle* h, float* agent, float* agent_grad, float* agent_sq, floa
 int ma_set_adam(ma_handle* h, const ma_adam* a);
 /* Running reward statistics [mean, var, count] (three device doubles, mq_set_reward_norm's semantics); NULL: off. */
 int ma_set_reward_norm(ma_handle* h, double* state);
+/* NULL switches back to the one-step actor-critic. Arguments are checked before any HIP call (MQ_ERR_ARG). */
+int ma_set_ppo(ma_handle* h, const ma_ppo* p);
 /* One train() on `batch` (t_len = max_t_filled). adam_step: the 1-based number of the Adam step this call applies
  * (ignored under RMSprop); the caller counts it, because a batch whose mask is empty applies nothing: it leaves every
- * bound buffer but stats untouched and writes stats[5] = 0, which the caller reads. */
+ * bound buffer but stats untouched and writes stats[5] = 0, which the caller reads. After ma_set_ppo the call applies
+ * `epochs` steps numbered adam_step, adam_step + 1, ..; an empty batch applies none of them and every row of
+ * epoch_stats is zero. */
 int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void* stream);
 /* target_critic <- critic (tau = 0 or tau >= 1 ... a hard copy), or target = target (1 - tau) + critic tau for
  * 0 < tau < 1 (soft_update_kernel). */
@@ -103,7 +121,9 @@ int64_t ma_critic_forward_workspace(const ma_config* cfg, int32_t batch_size, in
 int ma_critic_forward(const float* critic, const ma_config* cfg, const mq_replay* batch, int32_t t, float* v_out,
                       float* workspace, void* stream);
 /* 0 = V' (target critic) [T + 1][B*n]; 1 = V [T][B*n]; 2 = n-step returns [T][B*n]; 3 = pi [T][B*n][A];
- * 4 = dLoss/dlogits before the 1 / M scale [T * B*n][Ap], Ap = n_actions rounded up to 4 (pad columns zero). */
+ * 4 = dLoss/dlogits before the 1 / M scale [T * B*n][Ap], Ap = n_actions rounded up to 4 (pad columns zero).
+ * After a PPO step 1, 3 and 4 hold the last epoch's values, and 5 = old, epoch 0's log pi_u [T][B*n];
+ * 6 = the last epoch's ratio [T][B*n]. */
 int ma_copy_intermediate(ma_handle* h, int which, float* dst, int64_t* count, void* stream);
 int ma_last_plan(const ma_handle* h, ma_plan* out);
 

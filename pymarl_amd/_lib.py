@@ -46,6 +46,7 @@ EXPORTS = [
 MA_EXPORTS = [
     "ma_create", "ma_destroy", "ma_param_offsets", "ma_bind", "ma_set_adam", "ma_set_reward_norm", "ma_train_step",
     "ma_update_targets", "ma_critic_forward_workspace", "ma_critic_forward", "ma_copy_intermediate", "ma_last_plan",
+    "ma_set_ppo",
 ]
 
 # mc_allreduce_fn (include/mc_coma.h): int (*)(float* buf, int64_t count, void* stream, void* ctx)
@@ -124,10 +125,19 @@ class MAAdam(ctypes.Structure):
                 ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float)]
 
 
+class MAPpo(ctypes.Structure):
+    """ma_ppo: the PPO step's epochs and clip range, and the device buffer [epochs][MA_NSTATS] of per-epoch stats."""
+    _fields_ = [("epochs", ctypes.c_int32), ("eps_clip", ctypes.c_float), ("epoch_stats", ctypes.c_void_p)]
+
+
+PPO_STAT_CLIPPED = 15   # epoch_stats[k][15]: live rows whose surrogate gradient epoch k cut
+
+
 class MAPlan(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in (
         "rows", "rows_target", "k", "kp", "hidden", "vec16", "fwd_tiles", "vhead_blocks", "nstep_lds", "dv_blocks",
-        "ns_cw2", "ns_cw1", "policy_blocks", "policy_tail", "policy_lanes", "ap", "ns_aw1", "ns_aw2", "bwd_blocks", "reward_norm", "adam")]
+        "ns_cw2", "ns_cw1", "policy_blocks", "policy_tail", "policy_lanes", "ap", "ns_aw1", "ns_aw2", "bwd_blocks", "reward_norm", "adam",
+        "epochs", "hoisted")]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -252,6 +262,7 @@ def load(required=True):
         "ma_critic_forward": ([vp, ctypes.POINTER(MAConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp], ctypes.c_int),
         "ma_copy_intermediate": ([vp, ctypes.c_int, vp, ctypes.POINTER(i64), vp], ctypes.c_int),
         "ma_last_plan": ([vp, ctypes.POINTER(MAPlan)], ctypes.c_int),
+        "ma_set_ppo": ([vp, ctypes.POINTER(MAPpo)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

@@ -9,6 +9,7 @@
 #include "a2c_kernels.hpp"
 #include "coma_host.hpp"
 #include "optim_host.hpp"
+#include "ppo_kernels.hpp"
 
 struct ma_handle {
   ma_config cfg;
@@ -27,12 +28,15 @@ struct ma_handle {
   int* halt;
   // actor workspace
   float *dL, *dHo, *pi, *ppart, *slab_fc2, *red_tmp, *norm_part;
+  float *old_lp, *ratio;   // [T R] each, PPO: epoch 0's log-probabilities of the taken actions, the last epoch's ratio
   float* gbak;   // [Pa + MQ_NSUMS | Pc + MA_NTAIL] both gradient buffers before the reductions (a2c_gate_kernel)
   double* rbak;  // [3] the running reward statistics before reward_norm_kernel merged the batch into them
   int ns_max = 1, ndv_max = 1;   // slabs the workspace holds
   bool adam = false;
   ma_adam ad{};
   double* rew_state = nullptr;
+  bool ppo = false;   // ma_set_ppo: ma_train_step runs pp.epochs epochs (ppo_host.hpp)
+  ma_ppo pp{};
   ma_plan last{};
   int last_T = 0, last_R = 0;
 
@@ -111,6 +115,62 @@ int ma_apply(const ma_handle* h, float* p, float* g, float* m, float* v, int64_t
   MQ_HIP(hipGetLastError());
   return MQ_OK;
 }
+
+// The critic's backward GEMMs: dH1, then the split-K [dW2 | db2] and [dW1 | db1] slabs.
+int ma_critic_dw(const ma_handle* h, const ma_plan& pl, int64_t RT, hipStream_t s) {
+  const int Hc = h->Hc;
+  const float* oc = h->critic;
+  {
+    A2cDh1Prob p{h->dH2, oc + h->coff[MA_P_FC2_W], h->H1o, h->dH1, RT, Hc};
+    MQ_HIP(launch_gemm(p, (int)RT, Hc, 1, s));
+  }
+  {
+    A2cDwProb<64> p{h->dH2, Hc, h->H1o, Hc, Hc, h->slab_w2, RT, pl.ns_cw2};
+    MQ_HIP(launch_gemm(p, Hc, Hc, pl.ns_cw2, s));
+  }
+  {
+    A2cDwProb<128> p{h->dH1, Hc, h->X, h->Kp, h->K, h->slab_w1, RT, pl.ns_cw1};
+    MQ_HIP(launch_gemm(p, Hc, h->K, pl.ns_cw1, s));
+  }
+  return MQ_OK;
+}
+
+// The two-pass reduction of the critic's slabs and loss sums into cgrad [Pc | MA_NTAIL]; *nnorm = the norm partials
+// it left in cnorm_part.
+int ma_critic_reduce(const ma_handle* h, const ma_plan& pl, hipStream_t s, int* nnorm) {
+  const int Hc = h->Hc;
+  RedBuilder rb(h->cred_tmp);
+  rb.add(h->slab_w1, pl.ns_cw1, (int64_t)Hc * h->K + Hc, h->cgrad + h->coff[MA_P_FC1_W], true);
+  rb.add(h->slab_w2, pl.ns_cw2, (int64_t)Hc * Hc + Hc, h->cgrad + h->coff[MA_P_FC2_W], true);
+  rb.add(h->slab_w3, pl.dv_blocks, Hc + 1, h->cgrad + h->coff[MA_P_FC3_W], true);
+  rb.add(h->cpart, pl.dv_blocks, MA_NTAIL, h->cgrad + h->Pc, false);
+  if (rb.b2 > 4096) return set_err(MQ_ERR_ARG, "critic too large for the norm partial buffer");
+  hipLaunchKernelGGL(red_pass1_kernel, dim3(rb.b1), dim3(256), 0, s, rb.pl);
+  MQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(red_pass2_kernel, dim3(rb.b2), dim3(256), 0, s, rb.pl, h->cnorm_part);
+  MQ_HIP(hipGetLastError());
+  *nnorm = rb.b2;
+  return MQ_OK;
+}
+
+// Both applies after both backwards; an empty batch (M = 0) halts both (a2c_gate_kernel).
+int ma_gate_apply(const ma_handle* h, int nnorm_c, int nnorm_a, int64_t adam_step, hipStream_t s) {
+  const int64_t na = h->Pa + MQ_NSUMS, nc = h->Pc + MA_NTAIL;
+  hipLaunchKernelGGL(a2c_gate_kernel, dim3(1), dim3(A2C_GATE_THREADS), 0, s, (const float*)(h->cgrad + h->Pc), h->halt,
+                     h->stats, (const float*)h->gbak, h->agrad, na, h->cgrad, nc, h->rew_state,
+                     (const double*)h->rbak);
+  MQ_HIP(hipGetLastError());
+  int rc;
+  if ((rc = ma_apply(h, h->critic, h->cgrad, h->adam ? h->ad.critic_exp_avg : nullptr, h->csq, h->Pc, h->cnorm_part,
+                     nnorm_c, adam_step, h->stats, s)) ||
+      (rc = ma_apply(h, h->agent, h->agrad, h->adam ? h->ad.agent_exp_avg : nullptr, h->asq, h->Pa, h->norm_part,
+                     nnorm_a, adam_step, h->stats + 8, s)))
+    return rc;
+  return MQ_OK;
+}
+
+// ma_train_step after ma_set_ppo (ppo_host.hpp).
+int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStream_t s);
 
 }  // namespace
 
@@ -211,6 +271,7 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
       {"slab_fc2", (int64_t)kNsplitMax * (A * mq::H + A), &h->slab_fc2},
       {"red_tmp", red_tmp, &h->red_tmp},
       {"norm_part", 4096, &h->norm_part},
+      {"old_lp", RT, &h->old_lp}, {"ratio", RT, &h->ratio},
       {"gbak", h->Pa + MQ_NSUMS + h->Pc + MA_NTAIL, &h->gbak},
       {"rbak", 8, &rbak_f},   // three doubles (every row starts at a multiple of 64 floats: 8-byte aligned)
   };
@@ -278,12 +339,14 @@ int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void*
   if (rc || (rc = ma_check_replay(h->cfg, batch, "ma_train_step"))) return rc;
   if (h->adam && adam_step < 1) return set_err(MQ_ERR_ARG, "ma_train_step: adam_step is the 1-based step number (>= 1)");
   hipStream_t s = (hipStream_t)stream;
+  if (h->ppo) return ma_ppo_train(h, batch, adam_step, s);
   const ma_config& c = h->cfg;
   const int n = c.n_agents, Hc = h->Hc;
   const int B = batch->batch_size, Tp = batch->t_len, T = Tp - 1, R = B * n;
   const Rep rp = make_rep(batch);
   const ADims cd = ma_dims(c, B, Tp, batch->t_stride);
-  const ma_plan pl = a2c_plan(c, B, Tp, h->rew_state != nullptr, h->adam);
+  ma_plan pl = a2c_plan(c, B, Tp, h->rew_state != nullptr, h->adam);
+  pl.epochs = 1;
   const int64_t RT = (int64_t)T * R, RTp = (int64_t)Tp * R;
   // the plan's slabs against what ma_create allocated (max_batch / max_seq bound both)
   if (pl.ns_cw1 > h->ns_max || pl.ns_cw2 > h->ns_max || pl.dv_blocks > h->ndv_max || pl.ns_aw2 > kNsplitMax)
@@ -344,51 +407,20 @@ int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void*
                      h->ppart);
   MQ_HIP(hipGetLastError());
   // ---- critic backward: dH1, the split-K weight gradients, the two-pass reduction into cgrad [Pc | MA_NTAIL]
-  {
-    A2cDh1Prob p{h->dH2, oc + h->coff[MA_P_FC2_W], h->H1o, h->dH1, RT, Hc};
-    MQ_HIP(launch_gemm(p, (int)RT, Hc, 1, s));
-  }
-  {
-    A2cDwProb<64> p{h->dH2, Hc, h->H1o, Hc, Hc, h->slab_w2, RT, pl.ns_cw2};
-    MQ_HIP(launch_gemm(p, Hc, Hc, pl.ns_cw2, s));
-  }
-  {
-    A2cDwProb<128> p{h->dH1, Hc, h->X, h->Kp, h->K, h->slab_w1, RT, pl.ns_cw1};
-    MQ_HIP(launch_gemm(p, Hc, h->K, pl.ns_cw1, s));
-  }
+  if ((rc = ma_critic_dw(h, pl, RT, s))) return rc;
   // both gradient buffers as the caller left them: an empty batch puts them back (a2c_gate_kernel)
   const int64_t na = h->Pa + MQ_NSUMS, nc = h->Pc + MA_NTAIL;
   MQ_HIP(hipMemcpyAsync(h->gbak, h->agrad, (size_t)na * sizeof(float), hipMemcpyDeviceToDevice, s));
   MQ_HIP(hipMemcpyAsync(h->gbak + na, h->cgrad, (size_t)nc * sizeof(float), hipMemcpyDeviceToDevice, s));
   int nnorm_c;
-  {
-    RedBuilder rb(h->cred_tmp);
-    rb.add(h->slab_w1, pl.ns_cw1, (int64_t)Hc * h->K + Hc, h->cgrad + h->coff[MA_P_FC1_W], true);
-    rb.add(h->slab_w2, pl.ns_cw2, (int64_t)Hc * Hc + Hc, h->cgrad + h->coff[MA_P_FC2_W], true);
-    rb.add(h->slab_w3, pl.dv_blocks, Hc + 1, h->cgrad + h->coff[MA_P_FC3_W], true);
-    rb.add(h->cpart, pl.dv_blocks, MA_NTAIL, h->cgrad + h->Pc, false);
-    if (rb.b2 > 4096) return set_err(MQ_ERR_ARG, "critic too large for the norm partial buffer");
-    hipLaunchKernelGGL(red_pass1_kernel, dim3(rb.b1), dim3(256), 0, s, rb.pl);
-    MQ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(red_pass2_kernel, dim3(rb.b2), dim3(256), 0, s, rb.pl, h->cnorm_part);
-    MQ_HIP(hipGetLastError());
-    nnorm_c = rb.b2;
-  }
+  if ((rc = ma_critic_reduce(h, pl, s, &nnorm_c))) return rc;
   // ---- actor backward (the COMA learner's chain)
   int nnorm_a;
   if ((rc = actor_backward(ah, d, rp, Pa, L, w, RT, h->dL, h->Ap, h->slab_fc2, h->ppart, pl.policy_blocks, h->red_tmp,
                            h->norm_part, h->agrad, h->Pa, s, &nnorm_a)))
     return rc;
   // ---- both applies after both backwards; an empty batch (M = 0) halts both
-  hipLaunchKernelGGL(a2c_gate_kernel, dim3(1), dim3(A2C_GATE_THREADS), 0, s, (const float*)(h->cgrad + h->Pc), h->halt,
-                     h->stats, (const float*)h->gbak, h->agrad, na, h->cgrad, nc, h->rew_state,
-                     (const double*)h->rbak);
-  MQ_HIP(hipGetLastError());
-  if ((rc = ma_apply(h, h->critic, h->cgrad, h->adam ? h->ad.critic_exp_avg : nullptr, h->csq, h->Pc, h->cnorm_part,
-                     nnorm_c, adam_step, h->stats, s)) ||
-      (rc = ma_apply(h, h->agent, h->agrad, h->adam ? h->ad.agent_exp_avg : nullptr, h->asq, h->Pa, h->norm_part,
-                     nnorm_a, adam_step, h->stats + 8, s)))
-    return rc;
+  if ((rc = ma_gate_apply(h, nnorm_c, nnorm_a, adam_step, s))) return rc;
   h->last = pl;
   h->last_T = T;
   h->last_R = R;
@@ -420,6 +452,9 @@ int ma_copy_intermediate(ma_handle* h, int which, float* dst, int64_t* count, vo
     case 2: src = h->ret; cnt = TR; break;
     case 3: src = h->pi; cnt = TR * h->cfg.n_actions; break;
     case 4: src = h->dL; cnt = TR * h->Ap; break;
+    case 5: case 6:
+      if (h->last.hoisted < 1) return set_err(MQ_ERR_STATE, "the last train step was not a PPO step");
+      src = which == 5 ? h->old_lp : h->ratio; cnt = TR; break;
     default: return set_err(MQ_ERR_ARG, "unknown actor-critic intermediate id");
   }
   if (count) *count = cnt;

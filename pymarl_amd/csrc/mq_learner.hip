@@ -41,6 +41,7 @@
 #include "optim_host.hpp"
 #include "coma_host.hpp"
 #include "a2c_host.hpp"
+#include "ppo_host.hpp"
 
 namespace {
 
