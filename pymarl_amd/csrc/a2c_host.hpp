@@ -1,7 +1,7 @@
 // Host side of the actor-critic learner step (include/ma_a2c.h). As the COMA learner it keeps an
 // internal mq_handle (no mixer) for the agent's workspace and kernels and shares the actor's forward and backward with
-// it (coma_host.hpp actor_forward / actor_backward); the critic has its own workspace, sized once at ma_create from
-// max_batch / max_seq.
+// it (coma_host.hpp actor_forward / actor_backward, launched from a2c_plan's ActorPlan); the critic has its own
+// workspace, sized once at ma_create from max_batch / max_seq.
 #pragma once
 #include <cmath>
 
@@ -81,16 +81,6 @@ void ma_offsets(const ma_config& c, int64_t* off) {
   off[MA_P_COUNT] = o;
 }
 
-int ma_agent_config(const ma_config& c, mq_config* a) {
-  std::memset(a, 0, sizeof(*a));
-  a->n_agents = c.n_agents; a->n_actions = c.n_actions; a->obs_dim = c.obs_dim; a->state_dim = c.state_dim;
-  a->rnn_hidden_dim = c.rnn_hidden_dim; a->mixing_embed_dim = 0; a->mixer = MQ_MIXER_NONE; a->double_q = 0;
-  a->obs_last_action = c.obs_last_action; a->obs_agent_id = c.obs_agent_id; a->gamma = c.gamma_pow ? c.gamma_pow[1] : 0.0f;
-  a->lr = c.lr; a->optim_alpha = c.optim_alpha; a->optim_eps = c.optim_eps; a->grad_norm_clip = c.grad_norm_clip;
-  a->max_batch = c.max_batch; a->max_seq = c.max_seq;
-  return MQ_OK;
-}
-
 int ma_check_replay(const ma_config& c, const mq_replay* b, const char* who) {
   if (c.critic_type == MA_CRITIC_CV && !b->state) return set_err(MQ_ERR_ARG, std::string(who) + ": cv_critic needs batch.state");
   if (c.critic_type == MA_CRITIC_AC && !b->obs) return set_err(MQ_ERR_ARG, std::string(who) + ": ac_critic needs batch.obs");
@@ -144,12 +134,47 @@ int ma_critic_reduce(const ma_handle* h, const ma_plan& pl, hipStream_t s, int* 
   rb.add(h->slab_w2, pl.ns_cw2, (int64_t)Hc * Hc + Hc, h->cgrad + h->coff[MA_P_FC2_W], true);
   rb.add(h->slab_w3, pl.dv_blocks, Hc + 1, h->cgrad + h->coff[MA_P_FC3_W], true);
   rb.add(h->cpart, pl.dv_blocks, MA_NTAIL, h->cgrad + h->Pc, false);
-  if (rb.b2 > 4096) return set_err(MQ_ERR_ARG, "critic too large for the norm partial buffer");
-  hipLaunchKernelGGL(red_pass1_kernel, dim3(rb.b1), dim3(256), 0, s, rb.pl);
+  return launch_reduce(rb, h->cnorm_part, "critic", s, nnorm);
+}
+
+// fc1 and fc2 of one critic net with parameters P over `rows` rows of X, one CLinProbT launch per layer (A2cLin2's tile
+// code: bitwise what the two-net launch gives).
+int ma_critic_l12(const float* P, const int64_t* off, const ADims& d, const float* X, float* H1, float* H2, int64_t rows,
+                  hipStream_t s) {
+  const CLinProbT<64> l1 =
+      CLinProbT<64>{X, d.Kp, P + off[MA_P_FC1_W], P + off[MA_P_FC1_B], H1, rows, d.Hc, d.K, 1}.with_vec();
+  MQ_HIP(launch_gemm(l1, (int)rows, d.Hc, 1, s));
+  const CLinProbT<64> l2 =
+      CLinProbT<64>{H1, d.Hc, P + off[MA_P_FC2_W], P + off[MA_P_FC2_B], H2, rows, d.Hc, d.Hc, 1}.with_vec();
+  MQ_HIP(launch_gemm(l2, (int)rows, d.Hc, 1, s));
+  return MQ_OK;
+}
+
+// The returns: the rewards standardised first when asked for (reward[:, :T], all B T values; the statistics as they
+// were go to rbak, since an empty batch puts them back and so merges nothing into them), then the n-step pass.
+int ma_returns(const ma_handle* h, const ADims& cd, const Rep& rp, const ma_plan& pl, hipStream_t s) {
+  const ma_config& c = h->cfg;
+  if (h->rew_state) {
+    MQ_HIP(hipMemcpyAsync(h->rbak, h->rew_state, 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    const Dims dr = mq::make_dims(h->ah->cfg, cd.B, cd.Tp, cd.t_stride);   // dr.T = T, dr.M = T B
+    hipLaunchKernelGGL(reward_norm_kernel, dim3(1), dim3(RN_THREADS), 0, s, dr, rp, h->rew_state, h->RS);
+    MQ_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(a2c_nstep_kernel, dim3(cd.B), dim3(256), pl.nstep_lds, s, cd, rp, (const float*)h->Vt,
+                     (const float*)(h->rew_state ? h->RS : nullptr), (const float*)h->gpow, (int)c.q_nstep,
+                     (int)(c.add_value_last_step != 0), h->ret);
   MQ_HIP(hipGetLastError());
-  hipLaunchKernelGGL(red_pass2_kernel, dim3(rb.b2), dim3(256), 0, s, rb.pl, h->cnorm_part);
-  MQ_HIP(hipGetLastError());
-  *nnorm = rb.b2;
+  return MQ_OK;
+}
+
+// The step's plan and its actor's, checked against what ma_create allocated (max_batch / max_seq bound the slabs, and
+// PPO's old_lp and ratio) and against the n-step pass's LDS.
+int ma_step_plan(const ma_handle* h, int B, int Tp, ma_plan* pl, ActorPlan* ap) {
+  *pl = a2c_plan(h->cfg, B, Tp, h->rew_state != nullptr, h->adam, ap);
+  if (pl->ns_cw1 > h->ns_max || pl->ns_cw2 > h->ns_max || pl->dv_blocks > h->ndv_max || ap->ns_w2 > kNsplitMax)
+    return set_err(MQ_ERR_STATE, "actor-critic plan exceeds the workspace");
+  if (a2c_nstep_lds_bytes(Tp, h->cfg.n_agents) > kA2cNstepLdsMax)
+    return set_err(MQ_ERR_ARG, "episode too long for the LDS n-step return pass");
   return MQ_OK;
 }
 
@@ -209,12 +234,7 @@ int ma_critic_forward(const float* critic, const ma_config* cfg, const mq_replay
   ma_offsets(*cfg, off);
   hipLaunchKernelGGL(a2c_xin_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, d, rp, X, t0, M);
   MQ_HIP(hipGetLastError());
-  const CLinProbT<64> l1 =
-      CLinProbT<64>{X, d.Kp, critic + off[MA_P_FC1_W], critic + off[MA_P_FC1_B], H1, M, Hc, d.K, 1}.with_vec();
-  MQ_HIP(launch_gemm(l1, (int)M, Hc, 1, s));
-  const CLinProbT<64> l2 =
-      CLinProbT<64>{H1, Hc, critic + off[MA_P_FC2_W], critic + off[MA_P_FC2_B], H2, M, Hc, Hc, 1}.with_vec();
-  MQ_HIP(launch_gemm(l2, (int)M, Hc, 1, s));
+  if ((rc = ma_critic_l12(critic, off, d, X, H1, H2, M, s))) return rc;
   hipLaunchKernelGGL(a2c_vhead_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, (const float*)H2,
                      (const float*)nullptr, critic, critic, off[MA_P_FC3_W], off[MA_P_FC3_B], Hc, M, (int64_t)0, v_out,
                      (float*)nullptr, d.R, d.n, Tq);
@@ -228,8 +248,7 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
   int rc = ma_check_config(c, true);
   if (rc) return rc;
   if (c.max_batch * c.n_agents > MQ_INLINE_IDS * 64) return set_err(MQ_ERR_ARG, "max_batch * n_agents too large");
-  mq_config ac;
-  ma_agent_config(c, &ac);
+  const mq_config ac = agent_config(c, c.gamma_pow[1]);   // (ma_check_config: gamma_pow is not NULL)
   mq_handle* ah = nullptr;
   if ((rc = mq_create(&ac, &ah))) return rc;
   std::unique_ptr<ma_handle> h(new ma_handle());   // owns ah from here: a failure below frees both
@@ -264,13 +283,13 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
       {"dH2", RT * Hc, &h->dH2}, {"dH1", RT * Hc, &h->dH1},
       {"slab_w3", h->ndv_max * lw3, &h->slab_w3}, {"cpart", (int64_t)h->ndv_max * 8, &h->cpart},
       {"slab_w2", h->ns_max * lw2, &h->slab_w2}, {"slab_w1", h->ns_max * lw1, &h->slab_w1},
-      {"cred_tmp", cred_tmp, &h->cred_tmp}, {"cnorm_part", 4096, &h->cnorm_part},
+      {"cred_tmp", cred_tmp, &h->cred_tmp}, {"cnorm_part", kNormPartMax, &h->cnorm_part},
       {"halt", 8, nullptr, &h->halt},
       {"dL", RT * h->Ap, &h->dL}, {"dHo", RT * mq::H, &h->dHo}, {"pi", RT * A, &h->pi},
       {"ppart", ((RT + 3) / 4) * 8, &h->ppart},
       {"slab_fc2", (int64_t)kNsplitMax * (A * mq::H + A), &h->slab_fc2},
       {"red_tmp", red_tmp, &h->red_tmp},
-      {"norm_part", 4096, &h->norm_part},
+      {"norm_part", kNormPartMax, &h->norm_part},
       {"old_lp", RT, &h->old_lp}, {"ratio", RT, &h->ratio},
       {"gbak", h->Pa + MQ_NSUMS + h->Pc + MA_NTAIL, &h->gbak},
       {"rbak", 8, &rbak_f},   // three doubles (every row starts at a multiple of 64 floats: 8-byte aligned)
@@ -345,14 +364,11 @@ int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void*
   const int B = batch->batch_size, Tp = batch->t_len, T = Tp - 1, R = B * n;
   const Rep rp = make_rep(batch);
   const ADims cd = ma_dims(c, B, Tp, batch->t_stride);
-  ma_plan pl = a2c_plan(c, B, Tp, h->rew_state != nullptr, h->adam);
+  ma_plan pl;
+  ActorPlan ap;
+  if ((rc = ma_step_plan(h, B, Tp, &pl, &ap))) return rc;
   pl.epochs = 1;
   const int64_t RT = (int64_t)T * R, RTp = (int64_t)Tp * R;
-  // the plan's slabs against what ma_create allocated (max_batch / max_seq bound both)
-  if (pl.ns_cw1 > h->ns_max || pl.ns_cw2 > h->ns_max || pl.dv_blocks > h->ndv_max || pl.ns_aw2 > kNsplitMax)
-    return set_err(MQ_ERR_STATE, "actor-critic plan exceeds the workspace");
-  const size_t lds_ns = a2c_nstep_lds_bytes(Tp, n);
-  if (lds_ns > kA2cNstepLdsMax) return set_err(MQ_ERR_ARG, "episode too long for the LDS n-step return pass");
 
   // ---- critic forward: inputs, fc1 / fc2 of both nets (grid.z: 0 target over t <= T, 1 online over t < T), fc3
   hipLaunchKernelGGL(a2c_xin_kernel, dim3((unsigned)((RTp + 3) / 4)), dim3(256), 0, s, cd, rp, h->X, 0, RTp);
@@ -380,18 +396,7 @@ int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void*
   MQ_HIP(hipGetLastError());
   // ---- the agent's dims: the actor unrolls t < T only
   const Dims d = mq::make_dims(ah->cfg, B, T, batch->t_stride);   // d.Tp = T: d.RT() = T R
-  // ---- returns: rewards standardised first when asked for (reward[:, :T], all B T values), then the n-step pass
-  if (h->rew_state) {
-    // the statistics as they were: an empty batch puts them back (a2c_gate_kernel), so it merges nothing into them
-    MQ_HIP(hipMemcpyAsync(h->rbak, h->rew_state, 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    const Dims dr = mq::make_dims(ah->cfg, B, Tp, batch->t_stride);   // dr.T = T, dr.M = T B
-    hipLaunchKernelGGL(reward_norm_kernel, dim3(1), dim3(RN_THREADS), 0, s, dr, rp, h->rew_state, h->RS);
-    MQ_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(a2c_nstep_kernel, dim3(B), dim3(256), lds_ns, s, cd, rp, (const float*)h->Vt,
-                     (const float*)(h->rew_state ? h->RS : nullptr), (const float*)h->gpow, (int)c.q_nstep,
-                     (int)(c.add_value_last_step != 0), h->ret);
-  MQ_HIP(hipGetLastError());
+  if ((rc = ma_returns(h, cd, rp, pl, s))) return rc;
   hipLaunchKernelGGL(a2c_dv_kernel, dim3(pl.dv_blocks), dim3(256), 0, s, cd, rp, (const float*)h->ret,
                      (const float*)h->Vo, (const float*)h->H2o, oc + h->coff[MA_P_FC3_W], h->td, h->dH2, h->slab_w3,
                      h->cpart);
@@ -400,8 +405,7 @@ int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void*
   const Lay L = make_lay(ah);
   Work w = ah->w;
   w.dHo = h->dHo;
-  const float* Pa = h->agent;
-  if ((rc = actor_forward(ah, d, rp, Pa, L, w, RT, s))) return rc;
+  if ((rc = actor_forward(h, ap, d, rp, L, w, RT, s))) return rc;
   hipLaunchKernelGGL(a2c_policy_kernel, dim3(pl.policy_blocks), dim3(256), 0, s, d, rp, (const float*)w.Q,
                      (const float*)h->td, c.entropy_coef, (int)(c.mask_before_softmax != 0), h->Ap, h->dL, h->pi,
                      h->ppart);
@@ -416,9 +420,7 @@ int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void*
   if ((rc = ma_critic_reduce(h, pl, s, &nnorm_c))) return rc;
   // ---- actor backward (the COMA learner's chain)
   int nnorm_a;
-  if ((rc = actor_backward(ah, d, rp, Pa, L, w, RT, h->dL, h->Ap, h->slab_fc2, h->ppart, pl.policy_blocks, h->red_tmp,
-                           h->norm_part, h->agrad, h->Pa, s, &nnorm_a)))
-    return rc;
+  if ((rc = actor_backward(h, ap, d, rp, L, w, RT, pl.policy_blocks, s, &nnorm_a))) return rc;
   // ---- both applies after both backwards; an empty batch (M = 0) halts both
   if ((rc = ma_gate_apply(h, nnorm_c, nnorm_a, adam_step, s))) return rc;
   h->last = pl;

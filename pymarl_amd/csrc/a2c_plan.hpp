@@ -3,7 +3,7 @@
 // sizes the workspace from its upper bounds, and tests/host/a2c_plan_probe.cpp prints it.
 #pragma once
 #include "../../include/ma_a2c.h"
-#include "step_plan.hpp"
+#include "actor_plan.hpp"
 
 namespace mq {
 
@@ -22,7 +22,8 @@ inline size_t a2c_nstep_lds_bytes(int Tp, int n) { return (size_t)Tp * (n + 2) *
 // ever rounds this number down).
 inline int a2c_ns_max(int64_t RTmax) { return (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RTmax / 256)); }
 
-inline ma_plan a2c_plan(const ma_config& c, int B, int t_len, bool reward_norm, bool adam) {
+// `actor`, when given, receives the ActorPlan the actor's launches read: ns_aw1 / ns_aw2 / bwd_blocks report it.
+inline ma_plan a2c_plan(const ma_config& c, int B, int t_len, bool reward_norm, bool adam, ActorPlan* actor = nullptr) {
   ma_plan p{};
   const int R = B * c.n_agents, T = t_len - 1;
   const int64_t RT = (int64_t)T * R;
@@ -43,10 +44,11 @@ inline ma_plan a2c_plan(const ma_config& c, int B, int t_len, bool reward_norm, 
   p.policy_lanes = c.n_actions;
   p.ap = (c.n_actions + 3) & ~3;
   const int I = c.obs_dim + (c.obs_last_action ? c.n_actions : 0) + (c.obs_agent_id ? c.n_agents : 0);
-  p.ns_aw1 = split_k_slices(RT, (I + Dw1Prob::BN - 1) / Dw1Prob::BN);
-  p.ns_aw2 = split_k_slices(RT, 1);
-  const int rw = std::min(2, pick_rw(R, 256));
-  p.bwd_blocks = (R + rw - 1) / rw;
+  const ActorPlan ap = actor_plan(I, c.obs_dim, c.n_actions, c.n_agents, R, RT);
+  if (actor) *actor = ap;
+  p.ns_aw1 = ap.ns_w1;
+  p.ns_aw2 = ap.ns_w2;
+  p.bwd_blocks = ap.nblk_bwd;
   p.reward_norm = reward_norm ? 1 : 0;
   p.adam = adam ? 1 : 0;
   return p;

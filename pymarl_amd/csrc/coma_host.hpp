@@ -1,13 +1,14 @@
 // Host side of the COMA learner step (include/mc_coma.h). It shares the QMIX learner's error handling
 // (host_util.hpp), replay plumbing (learner_handle.hpp) and agent kernels. The agent (RNNAgent) forward / BPTT reuses
-// an internal mq_handle (no mixer) for its workspace; the critic has its own.
+// an internal mq_handle (no mixer) for its workspace; the critic has its own. What a step launches is coma_plan's
+// answer (coma_plan.hpp), fixed before the first launch; ComaStep launches it phase by phase and decides nothing.
 #pragma once
 #include "../../include/mc_coma.h"
-#include "coma_chain.hpp"
+#include "coma_plan.hpp"
 #include "gru_fwd_fused.hpp"
 #include "gru_kernels.hpp"
 #include "learner_handle.hpp"
-#include "reduce_plan.hpp"
+#include "optim_host.hpp"
 
 struct mc_handle {
   mc_config cfg;
@@ -96,99 +97,373 @@ mq_replay shard_replay(const mc_config& c, const mq_replay& b, int lo, int hi) {
   return s;
 }
 
-int mc_agent_config(const mc_config& c, mq_config* a) {
-  std::memset(a, 0, sizeof(*a));
-  a->n_agents = c.n_agents; a->n_actions = c.n_actions; a->obs_dim = c.obs_dim; a->state_dim = c.state_dim;
-  a->rnn_hidden_dim = c.rnn_hidden_dim; a->mixing_embed_dim = 0; a->mixer = MQ_MIXER_NONE; a->double_q = 0;
-  a->obs_last_action = c.obs_last_action; a->obs_agent_id = c.obs_agent_id; a->gamma = c.gamma; a->lr = c.lr;
-  a->optim_alpha = c.optim_alpha; a->optim_eps = c.optim_eps; a->grad_norm_clip = c.grad_norm_clip;
-  a->max_batch = c.max_batch; a->max_seq = c.max_seq;
-  return MQ_OK;
+// The internal agent handle's config (no mixer) from a COMA or an actor-critic config `c`.
+template <class C>
+mq_config agent_config(const C& c, float gamma) {
+  mq_config a{};
+  a.n_agents = c.n_agents; a.n_actions = c.n_actions; a.obs_dim = c.obs_dim; a.state_dim = c.state_dim;
+  a.rnn_hidden_dim = c.rnn_hidden_dim; a.mixer = MQ_MIXER_NONE;
+  a.obs_last_action = c.obs_last_action; a.obs_agent_id = c.obs_agent_id; a.gamma = gamma; a.lr = c.lr;
+  a.optim_alpha = c.optim_alpha; a.optim_eps = c.optim_eps; a.grad_norm_clip = c.grad_norm_clip;
+  a.max_batch = c.max_batch; a.max_seq = c.max_seq;
+  return a;
 }
 
-// The policy-gradient actor of the COMA and the actor-critic learners (a2c_host.hpp): the agent handle `ah` lends its
-// workspace `w` (w.dHo the caller's), Pa are the agent's parameters, RT = T R the actor's rows.
+// The policy-gradient actor of the COMA and the actor-critic learners (a2c_host.hpp). `h` is either learner's handle:
+// its agent handle h->ah lends the workspace `w` (w.dHo the learner's), h->agent are the agent's parameters, RT = T R
+// the actor's rows. Which kernels and how many slices is ActorPlan's answer (actor_plan.hpp).
 //
 // The agent unroll over t < T, online net only: the logits land in w.Q.
-int actor_forward(mq_handle* ah, const Dims& d, const Rep& rpa, const float* Pa, const Lay& L, const Work& w, int64_t RT,
-                  hipStream_t st) {
-  const int rw_fwd = pick_rw(d.R, 512);
-  if (rw_fwd == 1 && fused_fwd_ok(d.I, d.O, d.A, d.n, RT)) {
+template <class Hd>
+int actor_forward(const Hd* h, const ActorPlan& ap, const Dims& d, const Rep& rpa, const Lay& L, const Work& w,
+                  int64_t RT, hipStream_t st) {
+  const mq_handle* ah = h->ah;
+  const float* Pa = h->agent;
+  if (ap.fused_fwd) {
     launch_fwd_fused(dim3(d.R, 1), st, d, rpa, Pa, Pa, L, w);
     MQ_HIP(hipGetLastError());
-  } else {
-    Fc1Prob p1{d, rpa, Pa, Pa, ah->off[MQ_P_FC1_W], ah->off[MQ_P_FC1_B], w.X1, w.XIN, RT};
-    MQ_HIP(launch_gemm(p1, (int)RT, 2 * mq::H, 1, st));
-    GiProb p2{w.X1, Pa, Pa, ah->off[MQ_P_RNN_W_IH], ah->off[MQ_P_RNN_B_IH], w.GI, RT};
-    MQ_HIP(launch_gemm(p2, (int)RT, mq::G3, 1, st));
-    const dim3 grid((d.R + rw_fwd - 1) / rw_fwd, 1);
-    if (rw_fwd == 1) hipLaunchKernelGGL((gru_fwd_kernel<1, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-    else if (rw_fwd == 2) hipLaunchKernelGGL((gru_fwd_kernel<2, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-    else if (rw_fwd == 4) hipLaunchKernelGGL((gru_fwd_kernel<4, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-    else hipLaunchKernelGGL((gru_fwd_kernel<8, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-    MQ_HIP(hipGetLastError());
-    Fc2Prob p3{w.Hs, Pa, Pa, ah->off[MQ_P_FC2_W], ah->off[MQ_P_FC2_B], w.Q, RT, d.A};
-    MQ_HIP(launch_gemm(p3, (int)RT, d.A, 1, st));
+    return MQ_OK;
   }
+  Fc1Prob p1{d, rpa, Pa, Pa, ah->off[MQ_P_FC1_W], ah->off[MQ_P_FC1_B], w.X1, w.XIN, RT};
+  MQ_HIP(launch_gemm(p1, (int)RT, 2 * mq::H, 1, st));
+  GiProb p2{w.X1, Pa, Pa, ah->off[MQ_P_RNN_W_IH], ah->off[MQ_P_RNN_B_IH], w.GI, RT};
+  MQ_HIP(launch_gemm(p2, (int)RT, mq::G3, 1, st));
+  const dim3 grid((d.R + ap.rw_fwd - 1) / ap.rw_fwd, 1);
+  if (ap.rw_fwd == 1) hipLaunchKernelGGL((gru_fwd_kernel<1, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
+  else if (ap.rw_fwd == 2) hipLaunchKernelGGL((gru_fwd_kernel<2, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
+  else if (ap.rw_fwd == 4) hipLaunchKernelGGL((gru_fwd_kernel<4, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
+  else hipLaunchKernelGGL((gru_fwd_kernel<8, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
+  MQ_HIP(hipGetLastError());
+  Fc2Prob p3{w.Hs, Pa, Pa, ah->off[MQ_P_FC2_W], ah->off[MQ_P_FC2_B], w.Q, RT, d.A};
+  MQ_HIP(launch_gemm(p3, (int)RT, d.A, 1, st));
   return MQ_OK;
 }
 
-// From the policy kernel's dL [RT][Ap] (dense dLoss/dlogits) and its npol blocks of loss sums `ppart`: BPTT with the
-// dense output gradient, the split-K weight gradients, and the two-pass reduction into agrad [Pa_n | MQ_NSUMS];
-// *nnorm = the norm partials it left in norm_part.
-int actor_backward(mq_handle* ah, const Dims& d, const Rep& rpa, const float* Pa, const Lay& L, const Work& w,
-                   int64_t RT, const float* dL, int Ap, float* slab_fc2, float* ppart, int npol, float* red_tmp,
-                   float* norm_part, float* agrad, int64_t Pa_n, hipStream_t s, int* nnorm) {
+// From the policy kernel's h->dL [RT][Ap] (dense dLoss/dlogits) and its npol blocks of loss sums h->ppart: BPTT with
+// the dense output gradient, the split-K weight gradients, and the two-pass reduction into h->agrad [Pa | MQ_NSUMS];
+// *nnorm = the norm partials it left in h->norm_part.
+template <class Hd>
+int actor_backward(const Hd* h, const ActorPlan& ap, const Dims& d, const Rep& rpa, const Lay& L, const Work& w,
+                   int64_t RT, int npol, hipStream_t s, int* nnorm) {
+  const mq_handle* ah = h->ah;
+  const float* Pa = h->agent;
   const int A = d.A;
   {
-    DhoProb p{dL, Ap, A, Pa + ah->off[MQ_P_FC2_W], w.dHo, RT};
+    DhoProb p{h->dL, h->Ap, A, Pa + ah->off[MQ_P_FC2_W], w.dHo, RT};
     MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));
   }
-  const int rw_bwd = std::min(2, pick_rw(d.R, 256));
-  int nblk_bwd = (d.R + rw_bwd - 1) / rw_bwd;
   const size_t dyn = ((size_t)2 * d.A * mq::H + d.A) * sizeof(float);
-  if (rw_bwd == 1)
-    hipLaunchKernelGGL((gru_bwd_kernel<1, 0, true>), dim3(nblk_bwd), dim3(512), dyn, s, d, rpa, Pa, L, w, ah->len_rnn);
+  if (ap.rw_bwd == 1)
+    hipLaunchKernelGGL((gru_bwd_kernel<1, 0, true>), dim3(ap.nblk_bwd), dim3(512), dyn, s, d, rpa, Pa, L, w,
+                       ah->len_rnn);
   else
-    hipLaunchKernelGGL((gru_bwd_kernel<2, 0, true>), dim3(nblk_bwd), dim3(512), dyn, s, d, rpa, Pa, L, w, ah->len_rnn);
+    hipLaunchKernelGGL((gru_bwd_kernel<2, 0, true>), dim3(ap.nblk_bwd), dim3(512), dyn, s, d, rpa, Pa, L, w,
+                       ah->len_rnn);
   MQ_HIP(hipGetLastError());
   {
     Dx1Prob p{w.dGI, Pa + ah->off[MQ_P_RNN_W_IH], w.X1, w.dP1, RT};
     MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));
   }
-  int ns1;
   {
-    const int tiles = (d.I + Dw1Prob::BN - 1) / Dw1Prob::BN;
-    int ns = (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RT / 256));
-    ns = std::max(1, std::min(ns, (512 + tiles - 1) / tiles));
-    int64_t chunk = ((RT + ns - 1) / ns + GBK - 1) / GBK * GBK;
-    ns = (int)((RT + chunk - 1) / chunk);
-    ns1 = ns;
-    Dw1Prob p{d.I, w.dP1, w.XIN, w.slab_fc1, RT, ns};
-    MQ_HIP(launch_gemm(p, mq::H, d.I, ns, s));
+    Dw1Prob p{d.I, w.dP1, w.XIN, w.slab_fc1, RT, ap.ns_w1};
+    MQ_HIP(launch_gemm(p, mq::H, d.I, ap.ns_w1, s));
   }
-  int ns2;
   {
-    int ns = (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RT / 256));
-    int64_t chunk = ((RT + ns - 1) / ns + GBK - 1) / GBK * GBK;
-    ns = (int)((RT + chunk - 1) / chunk);
-    ns2 = ns;
-    Dw2Prob p{dL, Ap, A, w.Hs, slab_fc2, RT, ns};
-    MQ_HIP(launch_gemm(p, A, mq::H, ns, s));
+    Dw2Prob p{h->dL, h->Ap, A, w.Hs, h->slab_fc2, RT, ap.ns_w2};
+    MQ_HIP(launch_gemm(p, A, mq::H, ap.ns_w2, s));
   }
-  RedBuilder rb(red_tmp);
-  rb.add(w.slab_fc1, ns1, (int64_t)mq::H * d.I + mq::H, agrad + ah->off[MQ_P_FC1_W], true);
+  RedBuilder rb(h->red_tmp);
+  rb.add(w.slab_fc1, ap.ns_w1, (int64_t)mq::H * d.I + mq::H, h->agrad + ah->off[MQ_P_FC1_W], true);
   // W_ih .. b_hh: the prefix of each BPTT slab (its fc2 part is unused in the dense-dy mode)
-  rb.add(w.slab_rnn, nblk_bwd, ah->off[MQ_P_FC2_W] - ah->off[MQ_P_RNN_W_IH], agrad + ah->off[MQ_P_RNN_W_IH], true,
-         ah->len_rnn);
-  rb.add(slab_fc2, ns2, (int64_t)A * mq::H + A, agrad + ah->off[MQ_P_FC2_W], true);
-  rb.add(ppart, npol, MQ_NSUMS, agrad + Pa_n, false);
-  hipLaunchKernelGGL(red_pass1_kernel, dim3(rb.b1), dim3(256), 0, s, rb.pl);
+  rb.add(w.slab_rnn, ap.nblk_bwd, ah->off[MQ_P_FC2_W] - ah->off[MQ_P_RNN_W_IH], h->agrad + ah->off[MQ_P_RNN_W_IH],
+         true, ah->len_rnn);
+  rb.add(h->slab_fc2, ap.ns_w2, (int64_t)A * mq::H + A, h->agrad + ah->off[MQ_P_FC2_W], true);
+  rb.add(h->ppart, npol, MQ_NSUMS, h->agrad + h->Pa, false);
+  return launch_reduce(rb, h->norm_part, "agent", s, nnorm);
+}
+
+// The critic's three GEMMs over M rows of X [M][Kp] with parameters P at offsets `off` (mc_offsets): H1, H2, then
+// Q [M][A]. The target pass of a train step and mc_critic_forward.
+int critic_forward(const float* P, const int64_t* off, const CDims& cd, const float* X, float* H1, float* H2, float* Q,
+                   int64_t M, hipStream_t s) {
+  const CLinProbT<64> l1 =
+      CLinProbT<64>{X, cd.Kp, P + off[MC_P_FC1_W], P + off[MC_P_FC1_B], H1, M, CH, cd.Kc, 1}.with_vec();
+  MQ_HIP(launch_gemm(l1, (int)M, CH, 1, s));
+  const CLinProbT<64> l2 = CLinProbT<64>{H1, CH, P + off[MC_P_FC2_W], P + off[MC_P_FC2_B], H2, M, CH, CH, 1}.with_vec();
+  MQ_HIP(launch_gemm(l2, (int)M, CH, 1, s));
+  const CLinProbT<64> l3 = CLinProbT<64>{H2, CH, P + off[MC_P_FC3_W], P + off[MC_P_FC3_B], Q, M, cd.A, CH, 0}.with_vec();
+  MQ_HIP(launch_gemm(l3, (int)M, cd.A, 1, s));
+  return MQ_OK;
+}
+
+OptHP critic_hp(const mc_config& c) { return OptHP{c.critic_lr, c.optim_alpha, c.optim_eps, c.grad_norm_clip, 1}; }
+
+// The three-launch critic step's argument block.
+CritArgs crit_args(const mc_handle* h, const ComaPlan& pl, const CDims& cd, const Rep& rp) {
+  CritArgs a{};
+  a.d = cd; a.rp = rp;
+  a.P[0] = h->critic; a.P[1] = h->Pshadow; a.SQ[0] = h->csq; a.SQ[1] = h->SQshadow; a.G = h->cgrad;
+  a.o_w1 = h->coff[MC_P_FC1_W]; a.o_b1 = h->coff[MC_P_FC1_B]; a.o_w2 = h->coff[MC_P_FC2_W];
+  a.o_b2 = h->coff[MC_P_FC2_B]; a.o_w3 = h->coff[MC_P_FC3_W]; a.o_b3 = h->coff[MC_P_FC3_B]; a.Pc = h->Pc;
+  a.X = h->X; a.tgt = h->tgt; a.msum = h->msum; a.H1p = h->H1p; a.KS = pl.KS;
+  a.H1c = h->H1c; a.H2c = h->H2c; a.dH1c = h->dH1c; a.dH2c = h->dH2c; a.dqc = h->dqc; a.actc = h->actc;
+  a.qvals = h->qvals; a.cpart = h->cpart; a.cnorm = h->cnorm; a.crec = h->crec; a.cstate = h->cstate;
+  a.nhead = pl.nhead; a.nwgrad = pl.nwgrad;
+  a.hp = critic_hp(h->cfg);
+  return a;
+}
+
+// The persistent chain's argument block. cstate (zeroed by the step's first memset) carries its sync words; cnorm
+// (zeroed before the launch): [0, 2 G) the norm granules, [512, 512 + G) flagA, [768, 768 + NHEAD) flagB.
+CChain chain_args(const mc_handle* h, const ComaPlan& pl, const CDims& cd, const Rep& rp) {
+  CChain a{};
+  a.d = cd; a.rp = rp; a.P = h->critic; a.SQ = h->csq; a.G = h->cgrad;
+  a.o_w1 = h->coff[MC_P_FC1_W]; a.o_b1 = h->coff[MC_P_FC1_B]; a.o_w2 = h->coff[MC_P_FC2_W];
+  a.o_b2 = h->coff[MC_P_FC2_B]; a.o_w3 = h->coff[MC_P_FC3_W]; a.o_b3 = h->coff[MC_P_FC3_B]; a.Pc = h->Pc;
+  a.X = h->X; a.tgt = h->tgt; a.msum = h->msum; a.H1p = h->H1p;
+  a.H1x = h->H1c; a.H2x = h->H2c; a.dH2x = h->dH2c; a.dH1x = h->dH1c; a.dqx = h->dqc; a.actx = h->actc;
+  a.part = h->cpart; a.normg = (unsigned long long*)h->cnorm; a.GW = h->Pshadow; a.qvals = h->qvals;
+  a.crec = h->crec; a.cstate = h->cstate; a.sync = (unsigned*)(h->cstate + 2);
+  a.flagA = (unsigned*)(h->cnorm + 512);
+  a.flagB = (unsigned*)(h->cnorm + 768);
+  a.NK = pl.NK; a.NG = pl.NG; a.NHEAD = pl.nhead;
+  a.hp = critic_hp(h->cfg);
+  a.trace = h->chain_trace;
+  a.fault_wg = env_int("MQ_DIAG", "coma_fault", -1);   // test hook: a workgroup that stops flagging
+  return a;
+}
+
+// debug (MQ_DIAG coma_trace): per-phase spans of the chain's workgroup 0 (100 MHz clock), averaged over <= 16 steps
+int print_chain_trace(const mc_handle* h, hipStream_t s) {
+  unsigned long long hb[16 * 8];
+  MQ_HIP(hipMemcpyAsync(hb, h->chain_trace, sizeof(hb), hipMemcpyDeviceToHost, s));
+  MQ_HIP(hipStreamSynchronize(s));
+  double acc[8] = {0};
+  for (int i = 1; i < 15; ++i)
+    for (int k = 0; k < 8; ++k) acc[k] += 10.0 * (double)((k < 7 ? hb[i * 8 + k + 1] : hb[(i + 1) * 8]) - hb[i * 8 + k]);
+  std::fprintf(stderr, "coma_chain ns/step: A %.0f bar1 %.0f B %.0f bar2 %.0f C %.0f bar3 %.0f D %.0f next %.0f\n",
+               acc[0] / 14, acc[1] / 14, acc[2] / 14, acc[3] / 14, acc[4] / 14, acc[5] / 14, acc[6] / 14, acc[7] / 14);
+  return MQ_OK;
+}
+
+// One COMA train step's launches, phase by phase in stream order (mc_train_step calls them in this order). Which
+// kernels run, on which grids and streams, is the plan `pl`, fixed before the first launch.
+struct ComaStep {
+  mc_handle* h;
+  const ComaPlan pl;
+  const ComaMode m;
+  const CDims cd;
+  const Rep rp;    // the critic's batch: the whole one
+  const Rep rpa;   // the actor's: this rank's episodes under a replicated critic
+  const Dims d;    // the actor's dims (t < T)
+  const Lay L;
+  const Work w;
+  const float epsilon;
+  hipStream_t s;
+  bool chained = false;      // the chain's launch was accepted: critic_steps() has nothing to launch
+  bool actor_side = false;   // the actor's forward went out on the side stream
+  int nnorm = 0;             // the agent's norm partials in norm_part
+
+  int targets();
+  int critic_chain();
+  int critic_steps();
+  int actor();
+  int exchange();
+  int apply_and_stats();
+};
+
+ComaStep make_coma_step(mc_handle* h, const mq_replay* batch, const ComaPlan& pl, const ComaMode& m, float epsilon,
+                        hipStream_t s) {
+  const mc_config& c = h->cfg;
+  // replicated critic: the actor trains this rank's episodes only (the critic sees the whole batch)
+  mq_replay av = m.replicated ? shard_replay(c, *batch, m.shard_lo, m.shard_hi) : *batch;
+  av.t_len = pl.T;
+  const Rep rp = make_rep(batch);
+  Work w = h->ah->w;
+  w.dHo = h->dHo;
+  return ComaStep{h, pl, m, coma_dims(c, batch->batch_size, batch->t_len, batch->t_stride), rp,
+                  m.replicated ? make_rep(&av) : rp, mq::make_dims(h->ah->cfg, av.batch_size, av.t_len, av.t_stride),
+                  make_lay(h->ah), w, epsilon, s};
+}
+
+// Mask sums (summed over the ranks in exchange mode), the critic inputs X, the target critic over every stored step
+// (coma_learner.py:102), TD(lambda) (rl_utils.py:4-14); then what the critic steps start from: q_vals zeroed (skipped
+// steps keep 0) and, in exchange mode, the live steps on the host.
+int ComaStep::targets() {
+  const int T = pl.T, Tp = T + 1, R = pl.R;
+  if (m.timing) MQ_HIP(hipEventRecord(h->ev[0], s));
+  MQ_HIP(hipMemsetAsync(h->crec, 0, (size_t)T * 8 * sizeof(float), s));
+  MQ_HIP(hipMemsetAsync(h->cstate, 0, 8 * sizeof(int), s));
+  hipLaunchKernelGGL(coma_mask_kernel, dim3((T + 255) / 256), dim3(256), 0, s, cd, rp, h->msum);
   MQ_HIP(hipGetLastError());
-  if (rb.b2 > 4096) return set_err(MQ_ERR_ARG, "agent too large for the norm partial buffer");
-  hipLaunchKernelGGL(red_pass2_kernel, dim3(rb.b2), dim3(256), 0, s, rb.pl, norm_part);
+  int rc;
+  if (m.exchange) {   // global per-step mask sums: every rank normalises by them and skips the same steps
+    if (h->dp_scratch_n < 8LL * T) return set_err(MQ_ERR_ARG, "data-parallel scratch smaller than 8 * t_len");
+    if ((rc = mc_allreduce_ws(h, h->msum, T, s))) return rc;
+  }
+  hipLaunchKernelGGL(coma_xin_kernel, dim3(Tp * R), dim3(256), 0, s, cd, rp, h->X);
   MQ_HIP(hipGetLastError());
-  *nnorm = rb.b2;
+  if ((rc = critic_forward(h->tcritic, h->coff, cd, h->X, h->H1t, h->H2t, h->Qt, (int64_t)Tp * R, s))) return rc;
+  hipLaunchKernelGGL(coma_td_kernel, dim3(cd.B), dim3(256), pl.lds_td, s, cd, rp, h->Qt, h->tgt);
+  MQ_HIP(hipGetLastError());
+  MQ_HIP(hipMemsetAsync(h->qvals, 0, (size_t)T * R * cd.A * sizeof(float), s));
+  if (m.exchange) {   // the host needs the live steps to place the per-step exchanges (one synchronisation per train)
+    h->dp_msum.resize(T);
+    MQ_HIP(hipMemcpyAsync(h->dp_msum.data(), h->msum, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, s));
+    MQ_HIP(hipStreamSynchronize(s));
+  }
+  return MQ_OK;
+}
+
+// Every critic step (coma_learner.py:118-139) in one persistent launch where the plan says so, with the actor's agent
+// unroll beside it: the unroll reads nothing the critic writes, so it runs on the side stream in the CUs the chain
+// leaves idle. A refused launch clears chain_env and leaves the steps to critic_steps(), in this train() and after.
+int ComaStep::critic_chain() {
+  mq_handle* ah = h->ah;
+  if (pl.overlap) {
+    MQ_HIP(ensure_side(ah));
+    MQ_HIP(hipEventRecord(ah->ev_fork, s));   // before the chain: the side stream does not wait for it
+  }
+  if (m.timing) MQ_HIP(hipEventRecord(h->ev[1], s));
+  if (!pl.chain) return MQ_OK;
+  int rc;
+  if (env_item("MQ_DIAG", "coma_trace") &&
+      (rc = h->chain_trace.alloc(16 * 8, "hipMalloc(&h->chain_trace, 16 * 8 * sizeof(unsigned long long))")))
+    return rc;
+  const CChain cc = chain_args(h, pl, cd, rp);
+  MQ_HIP(hipMemsetAsync(h->cnorm, 0, 1024 * sizeof(float), s));   // norm granules and flags: no stale step tags
+  MQ_LDS(coma_chain_kernel, pl.lds_chain);
+  if (!h->chain_attr) {
+    MQ_HIP(hipFuncSetAttribute((const void*)coma_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)pl.lds_chain));
+    h->chain_attr = true;
+  }
+  // the chain updates the critic in place: keep the pre-train version, restored if a hand-off times out
+  // (apply_and_stats: the critic is put back before the actor's apply, the apply is skipped through its halt word, so
+  // the learner state is this train()'s starting state and COMALearner.train raises)
+  MQ_HIP(hipMemcpyAsync(h->Pbak, h->critic, (size_t)h->Pc * sizeof(float), hipMemcpyDeviceToDevice, s));
+  MQ_HIP(hipMemcpyAsync(h->Pbak + h->Pc, h->csq, (size_t)h->Pc * sizeof(float), hipMemcpyDeviceToDevice, s));
+  // A plain launch: the grid (cc_ok: at most one 512-thread workgroup per CU, NG <= the CU count) is resident
+  // by its size alone, which is all a cooperative launch would add a check for (MI355X_MICROARCH.md "Residency
+  // and cooperative launch": plain and cooperative launches give the same residency). Nothing else on the device
+  // waits on the chain, so a workgroup that starts late only delays it; every spin is bounded. The cooperative
+  // launch also cost 15-19 us of host time per train and, under rocprofv3, its dedicated HIP queue crashed the
+  // runtime's exit-time teardown (round 4: profiles/r04a_cfg5_rocprof_exit_crash.txt)
+  hipLaunchKernelGGL(coma_chain_kernel, dim3(pl.NG), dim3(CC_THREADS), pl.lds_chain, s, cc);
+  if (hipGetLastError() != hipSuccess) {   // the launch was refused: the three-launch path, from now on
+    h->chain_env = false;
+    return MQ_OK;
+  }
+  chained = true;
+  if (h->chain_trace && (rc = print_chain_trace(h, s))) return rc;
+  // Launched after the chain on a low-priority stream, so the chain's workgroups are normally dispatched first.
+  // That order is a heuristic across hardware queues, not a guarantee: if actor workgroups take CUs first, the
+  // chain's late workgroups start when they finish (the actor never waits on the chain), well inside the chain's
+  // spin bound (CC_SPIN_LIMIT polls, orders of magnitude longer than the actor unroll); a timeout would still be
+  // loud and leave the learner state unchanged (the restore)
+  if (pl.overlap) {
+    MQ_HIP(hipStreamWaitEvent(ah->side, ah->ev_fork, 0));
+    if ((rc = actor_forward(h, pl.actor, d, rpa, L, w, pl.actor_rows, ah->side))) return rc;
+    MQ_HIP(hipEventRecord(ah->ev_join, ah->side));
+    actor_side = true;
+  }
+  return MQ_OK;
+}
+
+// The critic's T sequential steps as three launches each and the last update's apply, where no chain ran; then, in
+// exchange mode, the per-step stat sums over the ranks.
+int ComaStep::critic_steps() {
+  const int T = pl.T;
+  int rc;
+  if (!chained) {
+    const CritArgs ca = crit_args(h, pl, cd, rp);
+    const dim3 l1_grid(pl.KS, CH / 16, (pl.R + kL1Rows - 1) / kL1Rows);
+    int live = 0;
+    for (int t = T - 1; t >= 0; --t) {
+      // live steps before t: exact in exchange mode, else assumed none was skipped (the kernels correct it)
+      const int Lexp = m.exchange ? live : T - 1 - t;
+      hipLaunchKernelGGL(coma_l1_kernel, l1_grid, dim3(256), pl.lds_l1, s, ca, t, Lexp);
+      hipLaunchKernelGGL(coma_head_kernel, dim3(pl.nhead), dim3(kHeadThreads), pl.lds_head, s, ca, t, Lexp);
+      hipLaunchKernelGGL(coma_wgrad_kernel, dim3(pl.nwgrad), dim3(256), 0, s, ca, t);
+      if (m.exchange && h->dp_msum[t] > 0.0f) {   // sum the step's unnormalised gradient, then its norm from the sum
+        ++live;
+        MQ_HIP(hipGetLastError());
+        if ((rc = mc_allreduce(h, h->cgrad, h->Pc, s))) return rc;
+        hipLaunchKernelGGL(sumsq_kernel, dim3(pl.nwgrad), dim3(256), 0, s, (const float*)h->cgrad, h->Pc, h->cnorm);
+      }
+    }
+    MQ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(coma_capply_kernel, dim3((int)std::min<int64_t>((h->Pc + 255) / 256, 512)), dim3(256), 0, s,
+                       ca);
+  }
+  MQ_HIP(hipGetLastError());
+  if (m.exchange) {   // per-step critic stat sums; the replicated fields (mask sum, norm, live flag) come from rank 0
+    if (h->dp_rank != 0) hipLaunchKernelGGL(coma_dp_crec_kernel, dim3((T + 255) / 256), dim3(256), 0, s, h->crec, T);
+    MQ_HIP(hipGetLastError());
+    if ((rc = mc_allreduce_ws(h, h->crec, 8LL * T, s))) return rc;
+  }
+  if (m.timing) MQ_HIP(hipEventRecord(h->ev[2], s));
+  return MQ_OK;
+}
+
+// The agent unroll over t < T (coma_learner.py:52-57; joined here if it ran beside the chain), the policy, baseline,
+// advantage, loss sums and dLogits (coma_learner.py:59-77, basic_controller.py:53-73), then the BPTT with the dense
+// output gradient, the weight gradients and their reduction.
+int ComaStep::actor() {
+  int rc;
+  if (actor_side) MQ_HIP(hipStreamWaitEvent(s, h->ah->ev_join, 0));
+  else if ((rc = actor_forward(h, pl.actor, d, rpa, L, w, pl.actor_rows, s))) return rc;
+  const float eps = epsilon, omeps = (float)(1.0 - (double)epsilon);
+  hipLaunchKernelGGL(coma_policy_kernel, dim3(pl.npol), dim3(256), 0, s, d, rpa, (const float*)w.Q,
+                     (const float*)h->qvals, pl.R, pl.qv_r0, eps, omeps, (int)(h->cfg.mask_before_softmax != 0), h->Ap,
+                     h->dL, h->pi, h->ppart);
+  MQ_HIP(hipGetLastError());
+  return actor_backward(h, pl.actor, d, rpa, L, w, pl.actor_rows, pl.npol, s, &nnorm);
+}
+
+// Data parallel: the agent gradient + loss / mask sums over the ranks, then the norm partials of the summed gradient.
+// Under a replicated critic the chain's error word rides in the agent sums' spare slot 7 (0 on success), so any rank's
+// chain failure halts every rank: all roll back, skip the apply and raise.
+int ComaStep::exchange() {
+  if (!m.exchange && !m.replicated) return MQ_OK;
+  const bool halt = m.replicated && chained;
+  if (halt) {
+    hipLaunchKernelGGL(coma_halt_to_sum_kernel, dim3(1), dim3(64), 0, s, (const int*)(h->cstate + 3),
+                       h->agrad + h->Pa + 7);
+    MQ_HIP(hipGetLastError());
+  }
+  const int rc = mc_allreduce(h, h->agrad, h->Pa + MQ_NSUMS, s);
+  if (rc) return rc;
+  if (halt) {
+    hipLaunchKernelGGL(coma_sum_to_halt_kernel, dim3(1), dim3(64), 0, s, (const float*)(h->agrad + h->Pa + 7),
+                       h->cstate + 3);
+    MQ_HIP(hipGetLastError());
+  }
+  nnorm = 256;
+  hipLaunchKernelGGL(sumsq_kernel, dim3(nnorm), dim3(256), 0, s, (const float*)h->agrad, h->Pa, h->norm_part);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+// A timed-out chain (on any rank, when replicated) puts the critic back to its pre-train version; the agent's RMSprop
+// step (none after such a failure: its halt word); the stats.
+int ComaStep::apply_and_stats() {
+  const mc_config& c = h->cfg;
+  if (chained) {
+    hipLaunchKernelGGL(coma_chain_restore_kernel, dim3(64), dim3(256), 0, s, (const int*)h->cstate,
+                       (const float*)h->Pbak, h->critic, h->csq, h->Pc);
+    MQ_HIP(hipGetLastError());
+  }
+  const OptHP hp{c.lr, c.optim_alpha, c.optim_eps, c.grad_norm_clip, 1};
+  const int blocks = (int)std::min<int64_t>((h->Pa + 255) / 256, 1024);
+  hipLaunchKernelGGL(apply_kernel, dim3(blocks), dim3(256), 0, s, h->agent, h->agrad, h->asq, h->Pa,
+                     (const float*)h->norm_part, nnorm, hp, h->stats + 8,
+                     chained ? (const int*)(h->cstate + 3) : (const int*)nullptr);
+  MQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(coma_stats_kernel, dim3(1), dim3(64), 0, s, (const float*)h->crec, pl.T, (const int*)h->cstate,
+                     h->stats);
+  MQ_HIP(hipGetLastError());
+  if (m.timing) MQ_HIP(hipEventRecord(h->ev[3], s));
   return MQ_OK;
 }
 
@@ -198,10 +473,9 @@ extern "C" {
 
 int64_t mc_critic_forward_workspace(const mc_config* cfg, int32_t batch_size, int32_t t_count) {
   if (!cfg || batch_size < 1 || t_count < 1) return -1;
-  const int n = cfg->n_agents, A = cfg->n_actions;
-  const int64_t Kp = ((int64_t)cfg->state_dim + cfg->obs_dim + 2 * n * A + n + 3) & ~int64_t(3);
-  const int64_t M = (int64_t)t_count * batch_size * n;
-  return align_up(M * Kp) + 2 * align_up(M * CH) + align_up(M * A);
+  const int64_t Kp = (coma_k(*cfg) + 3) & ~3;
+  const int64_t M = (int64_t)t_count * batch_size * cfg->n_agents;
+  return align_up(M * Kp) + 2 * align_up(M * CH) + align_up(M * cfg->n_actions);
 }
 
 int mc_critic_forward(const float* critic, const mc_config* cfg, const mq_replay* batch, int32_t t, float* q_out,
@@ -215,35 +489,23 @@ int mc_critic_forward(const float* critic, const mc_config* cfg, const mq_replay
   if (batch->ep_ids_host && batch->batch_size > MQ_INLINE_IDS && !batch->ep_ids)
     return set_err(MQ_ERR_ARG, "mc_critic_forward: more than MQ_INLINE_IDS episodes need device ids");
   hipStream_t s = (hipStream_t)stream;
-  const int n = cfg->n_agents, A = cfg->n_actions, B = batch->batch_size, R = B * n;
   const int Tq = t < 0 ? batch->t_len : 1, t0 = t < 0 ? 0 : t;
-  CDims cd{};
-  cd.n = n; cd.A = A; cd.O = cfg->obs_dim; cd.S = cfg->state_dim;
-  cd.Kc = cfg->state_dim + cfg->obs_dim + 2 * n * A + n;
-  cd.Kp = (cd.Kc + 3) & ~3;
-  cd.R = R; cd.B = B; cd.Tp = batch->t_len; cd.T = batch->t_len - 1; cd.t_stride = batch->t_stride;
-  cd.dR = make_fastdiv((uint32_t)R);
-  cd.dN = make_fastdiv((uint32_t)n);
+  const CDims cd = coma_dims(*cfg, batch->batch_size, batch->t_len, batch->t_stride);
   const Rep rp = make_rep(batch);
-  const int64_t M = (int64_t)Tq * R;
+  const int64_t M = (int64_t)Tq * cd.R;
   float* X = workspace;
   float* H1 = X + align_up(M * cd.Kp);
   float* H2 = H1 + align_up(M * CH);
   float* Q = H2 + align_up(M * CH);
-  // offsets of fc1.weight .. fc3.bias (MC_P_* order)
-  const int64_t o_w1 = 0, o_b1 = (int64_t)CH * cd.Kc, o_w2 = o_b1 + CH, o_b2 = o_w2 + (int64_t)CH * CH,
-                o_w3 = o_b2 + CH, o_b3 = o_w3 + (int64_t)A * CH;
+  int64_t off[MC_P_COUNT + 1];
+  mc_offsets(*cfg, off);
   hipLaunchKernelGGL(coma_xin_kernel, dim3((unsigned)M), dim3(256), 0, s, cd, rp, X, t0);
   MQ_HIP(hipGetLastError());
-  const CLinProbT<64> l1 = CLinProbT<64>{X, cd.Kp, critic + o_w1, critic + o_b1, H1, M, CH, cd.Kc, 1}.with_vec();
-  MQ_HIP(launch_gemm(l1, (int)M, CH, 1, s));
-  const CLinProbT<64> l2 = CLinProbT<64>{H1, CH, critic + o_w2, critic + o_b2, H2, M, CH, CH, 1}.with_vec();
-  MQ_HIP(launch_gemm(l2, (int)M, CH, 1, s));
-  const CLinProbT<64> l3 = CLinProbT<64>{H2, CH, critic + o_w3, critic + o_b3, Q, M, A, CH, 0}.with_vec();
-  MQ_HIP(launch_gemm(l3, (int)M, A, 1, s));
-  const int64_t tot = M * A;
+  const int rc = critic_forward(critic, off, cd, X, H1, H2, Q, M, s);
+  if (rc) return rc;
+  const int64_t tot = M * cd.A;
   hipLaunchKernelGGL(coma_q_layout_kernel, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 4096)), dim3(256), 0, s,
-                     (const float*)Q, q_out, Tq, B, n, A);
+                     (const float*)Q, q_out, Tq, cd.B, cd.n, cd.A);
   MQ_HIP(hipGetLastError());
   return MQ_OK;
 }
@@ -253,8 +515,7 @@ int mc_create(const mc_config* cfg, mc_handle** out) {
   const mc_config& c = *cfg;
   if (c.n_actions < 1 || c.n_actions > 64) return set_err(MQ_ERR_ARG, "n_actions must be in [1, 64]");
   if (c.max_batch * c.n_agents > MQ_INLINE_IDS * 64) return set_err(MQ_ERR_ARG, "max_batch * n_agents too large");
-  mq_config ac;
-  mc_agent_config(c, &ac);
+  const mq_config ac = agent_config(c, c.gamma);
   mq_handle* ah = nullptr;
   int rc = mq_create(&ac, &ah);
   if (rc) return rc;
@@ -265,19 +526,14 @@ int mc_create(const mc_config* cfg, mc_handle** out) {
   for (int i = 0; i <= MQ_P_COUNT; ++i) h->aoff[i] = ah->off[i];
   h->Pa = ah->P;
   const int n = c.n_agents, A = c.n_actions;
-  h->Kc = c.state_dim + c.obs_dim + 2 * n * A + n;   // coma.py:61-70
+  h->Kc = coma_k(c);
   h->Kp = (h->Kc + 3) & ~3;
   h->Ap = (A + 3) & ~3;
-  const int64_t sz[MC_P_COUNT] = {(int64_t)CH * h->Kc, CH, (int64_t)CH * CH, CH, (int64_t)A * CH, A};
-  int64_t o = 0;
-  for (int i = 0; i < MC_P_COUNT; ++i) { h->coff[i] = o; o += sz[i]; }
-  h->coff[MC_P_COUNT] = o;
-  h->Pc = o;
+  mc_offsets(c, h->coff);
+  h->Pc = h->coff[MC_P_COUNT];
 
   const int64_t Tp = c.max_seq, R = (int64_t)c.max_batch * n, T = Tp - 1;
   const int64_t RTa = T * R;   // actor rows (T steps)
-  const int64_t nwg = 8 * ((h->Kc + 1 + 63) / 64) + 24 + 3 * ((A + 15) / 16) + 1, nhead = (R + 15) / 16;
-  const int64_t ns2 = kNsplitMax;
   const int64_t red_tmp = kRedZ * ((int64_t)mq::H * h->I + mq::H) + kRedZ * h->ah->len_rnn +
                           kRedZ * (A * mq::H + A) + kRedZ * 8;
   const WsTable ws = {
@@ -286,21 +542,22 @@ int mc_create(const mc_config* cfg, mc_handle** out) {
       {"Qt", Tp * R * A, &h->Qt},
       {"tgt", T * R, &h->tgt}, {"msum", T, &h->msum},
       // three-launch l1 or chain phase A
-      {"H1p", (int64_t)std::max(l1_slices(h->Kp), cc_nk(h->Kc)) * R * CH, &h->H1p},
+      {"H1p", coma_h1p_slices(h->Kc) * R * CH, &h->H1p},
       {"H1c", R * CH, &h->H1c}, {"H2c", R * CH, &h->H2c}, {"dH1c", R * CH, &h->dH1c}, {"dH2c", R * CH, &h->dH2c},
       {"dqc", R, &h->dqc}, {"actc", R, nullptr, &h->actc},
       {"qvals", T * R * A, &h->qvals},
-      {"cpart", nhead * 8, &h->cpart},
-      {"cnorm", std::max<int64_t>(nwg, 1024), &h->cnorm},   // chain: 256 8-B granules + flags
+      {"cpart", (int64_t)coma_heads((int)R) * 8, &h->cpart},
+      // chain: 256 8-B granules + flags
+      {"cnorm", std::max<int64_t>(coma_wgrad_blocks(h->Kc, A), 1024), &h->cnorm},
       {"crec", T * 8, &h->crec},
       // shadow params / square_avg (the chain's gradient exchange: Pshadow)
       {"Pshadow", h->Pc, &h->Pshadow}, {"SQshadow", h->Pc, &h->SQshadow},
       {"cstate", 8, nullptr, &h->cstate},   // + the critic chain's sync words
       {"dL", RTa * h->Ap, &h->dL}, {"dHo", RTa * mq::H, &h->dHo}, {"pi", RTa * A, &h->pi},
       {"ppart", ((RTa + 3) / 4) * 8, &h->ppart},
-      {"slab_fc2", ns2 * (A * mq::H + A), &h->slab_fc2},
+      {"slab_fc2", (int64_t)kNsplitMax * (A * mq::H + A), &h->slab_fc2},
       {"red_tmp", red_tmp, &h->red_tmp},
-      {"norm_part", 4096, &h->norm_part},
+      {"norm_part", kNormPartMax, &h->norm_part},
       {"Pbak", 2 * h->Pc, &h->Pbak},
   };
   if ((rc = ws_carve(h->ws, ws, "COMA workspace hipMalloc"))) return rc;
@@ -339,23 +596,8 @@ int mc_bind(mc_handle* h, float* agent, float* agent_grad, float* agent_sq, floa
 
 int mc_train_step(mc_handle* h, const mq_replay* batch, float epsilon, void* stream) {
   if (!h || !h->agent) return set_err(MQ_ERR_STATE, "mc_train_step before mc_bind");
-  mq_handle* ah = h->ah;
-  int rc = check_batch(ah, batch);
+  int rc = check_batch(h->ah, batch);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const mc_config& c = h->cfg;
-  const int n = c.n_agents, A = c.n_actions;
-  const int Tp = batch->t_len, T = Tp - 1, R = batch->batch_size * n;
-  const Rep rp = make_rep(batch);
-
-  CDims cd;
-  cd.n = n; cd.A = A; cd.O = c.obs_dim; cd.S = c.state_dim; cd.Kc = h->Kc; cd.Kp = h->Kp; cd.R = R;
-  cd.B = batch->batch_size; cd.Tp = Tp; cd.T = T; cd.t_stride = batch->t_stride;
-  cd.lg = (float)((double)c.td_lambda * (double)c.gamma);
-  cd.og = (float)((1.0 - (double)c.td_lambda) * (double)c.gamma);
-  cd.dR = make_fastdiv((uint32_t)R);
-  cd.dN = make_fastdiv((uint32_t)n);
-
   const bool repl = h->shard_hi > h->shard_lo;
   if (repl && (h->shard_lo < 0 || h->shard_hi > batch->batch_size))
     return set_err(MQ_ERR_ARG, "actor shard [" + std::to_string(h->shard_lo) + ", " + std::to_string(h->shard_hi) +
@@ -363,234 +605,20 @@ int mc_train_step(mc_handle* h, const mq_replay* batch, float epsilon, void* str
   if (repl && !h->dp_fn)
     return set_err(MQ_ERR_STATE, "a replicated critic needs an all-reduce for the actor (mc_set_data_parallel / "
                                  "mc_comm_attach)");
-  if (h->timing) MQ_HIP(hipEventRecord(h->ev[0], s));
-  MQ_HIP(hipMemsetAsync(h->crec, 0, (size_t)T * 8 * sizeof(float), s));
-  MQ_HIP(hipMemsetAsync(h->cstate, 0, 8 * sizeof(int), s));
-  hipLaunchKernelGGL(coma_mask_kernel, dim3((T + 255) / 256), dim3(256), 0, s, cd, rp, h->msum);
-  MQ_HIP(hipGetLastError());
-  const bool dp = h->dp_fn != nullptr && !repl;   // exchange mode: the critic steps are summed over the ranks
-  if (dp) {   // global per-step mask sums: every rank normalises by them and skips the same steps
-    if (h->dp_scratch_n < 8LL * T) return set_err(MQ_ERR_ARG, "data-parallel scratch smaller than 8 * t_len");
-    rc = mc_allreduce_ws(h, h->msum, T, s);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(coma_xin_kernel, dim3(Tp * R), dim3(256), 0, s, cd, rp, h->X);
-  MQ_HIP(hipGetLastError());
-  // target critic over every stored step (coma_learner.py:102), then TD(lambda) (rl_utils.py:4-14)
-  {
-    const int64_t M = (int64_t)Tp * R;
-    const float* tc = h->tcritic;
-    const CLinProbT<64> l1 =
-        CLinProbT<64>{h->X, h->Kp, tc + h->coff[MC_P_FC1_W], tc + h->coff[MC_P_FC1_B], h->H1t, M, CH, h->Kc, 1}
-            .with_vec();
-    MQ_HIP(launch_gemm(l1, (int)M, CH, 1, s));
-    const CLinProbT<64> l2 =
-        CLinProbT<64>{h->H1t, CH, tc + h->coff[MC_P_FC2_W], tc + h->coff[MC_P_FC2_B], h->H2t, M, CH, CH, 1}.with_vec();
-    MQ_HIP(launch_gemm(l2, (int)M, CH, 1, s));
-    const CLinProbT<64> l3 =
-        CLinProbT<64>{h->H2t, CH, tc + h->coff[MC_P_FC3_W], tc + h->coff[MC_P_FC3_B], h->Qt, M, A, CH, 0}.with_vec();
-    MQ_HIP(launch_gemm(l3, (int)M, A, 1, s));
-  }
-  const size_t lds_td = (size_t)Tp * (n + 3) * sizeof(float);
-  if (lds_td > 160 * 1024 || n > 256) return set_err(MQ_ERR_ARG, "episode too long for the LDS TD(lambda) pass");
-  hipLaunchKernelGGL(coma_td_kernel, dim3(batch->batch_size), dim3(256), lds_td, s, cd, rp, h->Qt, h->tgt);
-  MQ_HIP(hipGetLastError());
-
-  // the critic's T sequential steps (coma_learner.py:118-139)
-  CritArgs ca;
-  ca.d = cd; ca.rp = rp;
-  ca.P[0] = h->critic; ca.P[1] = h->Pshadow; ca.SQ[0] = h->csq; ca.SQ[1] = h->SQshadow; ca.G = h->cgrad;
-  ca.o_w1 = h->coff[MC_P_FC1_W]; ca.o_b1 = h->coff[MC_P_FC1_B]; ca.o_w2 = h->coff[MC_P_FC2_W];
-  ca.o_b2 = h->coff[MC_P_FC2_B]; ca.o_w3 = h->coff[MC_P_FC3_W]; ca.o_b3 = h->coff[MC_P_FC3_B]; ca.Pc = h->Pc;
-  ca.X = h->X; ca.tgt = h->tgt; ca.msum = h->msum; ca.H1p = h->H1p; ca.KS = l1_slices(h->Kp); ca.H1c = h->H1c; ca.H2c = h->H2c; ca.dH1c = h->dH1c;
-  ca.dH2c = h->dH2c; ca.dqc = h->dqc; ca.actc = h->actc; ca.qvals = h->qvals; ca.cpart = h->cpart;
-  ca.cnorm = h->cnorm; ca.crec = h->crec; ca.cstate = h->cstate;
-  ca.nhead = (R + 15) / 16;
-  ca.nwgrad = wgrad_blocks(cd);
-  ca.hp = OptHP{c.critic_lr, c.optim_alpha, c.optim_eps, c.grad_norm_clip, 1};
-  const int A16 = (A + 15) / 16 * 16;
-  const size_t lds_l1 = (size_t)(16 + kL1Rows) * (KW + 1) * sizeof(float);
-  const size_t lds_head = ((size_t)(CH + A16 + 48) * (CH + 1) + 16 * (A16 + 1) + CH + A16) * sizeof(float);
-  if (lds_l1 > 160 * 1024 || lds_head > 160 * 1024)
-    return set_err(MQ_ERR_ARG, "critic input width or n_actions too large for the LDS-staged critic step");
-  MQ_HIP(hipMemsetAsync(h->qvals, 0, (size_t)T * R * A * sizeof(float), s));   // skipped steps keep q_vals = 0
-  if (dp) {   // the host needs the live steps to place the per-step exchanges (one synchronisation per train)
-    h->dp_msum.resize(T);
-    MQ_HIP(hipMemcpyAsync(h->dp_msum.data(), h->msum, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, s));
-    MQ_HIP(hipStreamSynchronize(s));
-  }
-  // ---- the actor's agent unroll over t < T (coma_learner.py:52-57), online net only. It reads nothing the critic
-  // writes, so beside the persistent chain it runs on the side stream in the CUs the chain leaves idle.
-  // replicated critic: the actor trains this rank's episodes only (the critic above saw the whole batch)
-  mq_replay av = repl ? shard_replay(c, *batch, h->shard_lo, h->shard_hi) : *batch;
-  av.t_len = T;
-  const Rep rpa = repl ? make_rep(&av) : rp;
-  const int qv_r0 = repl ? h->shard_lo * n : 0;   // this rank's first row in the critic's [T][B n][A] Q values
-  Dims d = mq::make_dims(ah->cfg, av.batch_size, av.t_len, av.t_stride);
-  const Lay L = make_lay(ah);
-  Work w = ah->w;
-  w.dHo = h->dHo;
-  const int64_t RT = (int64_t)T * d.R;   // the actor's rows (its shard under a replicated critic)
-  const float* Pa = h->agent;
-  auto agent_forward = [&](hipStream_t st) -> int { return actor_forward(ah, d, rpa, Pa, L, w, RT, st); };
-  // MQ_PLAN coma_overlap=0: the actor's agent unroll stays on the caller's stream
-  const bool try_overlap = !dp && !h->timing && plan_int("coma_overlap", 1) != 0 && h->chain_env &&
-                           cc_ok(R, A, h->Kc, h->num_cu);
-  if (try_overlap) {
-    MQ_HIP(ensure_side(ah));
-    MQ_HIP(hipEventRecord(ah->ev_fork, s));   // before the chain: the side stream does not wait for it
-  }
-  bool actor_side = false;
-  if (h->timing) MQ_HIP(hipEventRecord(h->ev[1], s));
-  bool chained = false;
-  if (!dp && h->chain_env && cc_ok(R, A, h->Kc, h->num_cu)) {   // every critic step in one persistent launch
-    CChain cc;
-    cc.d = cd; cc.rp = rp; cc.P = h->critic; cc.SQ = h->csq; cc.G = h->cgrad;
-    cc.o_w1 = ca.o_w1; cc.o_b1 = ca.o_b1; cc.o_w2 = ca.o_w2; cc.o_b2 = ca.o_b2; cc.o_w3 = ca.o_w3; cc.o_b3 = ca.o_b3;
-    cc.Pc = h->Pc; cc.X = h->X; cc.tgt = h->tgt; cc.msum = h->msum; cc.H1p = h->H1p;
-    cc.H1x = h->H1c; cc.H2x = h->H2c; cc.dH2x = h->dH2c; cc.dH1x = h->dH1c; cc.dqx = h->dqc; cc.actx = h->actc;
-    cc.part = h->cpart; cc.normg = (unsigned long long*)h->cnorm; cc.GW = h->Pshadow; cc.qvals = h->qvals;
-    cc.crec = h->crec; cc.cstate = h->cstate; cc.sync = (unsigned*)(h->cstate + 2);   // zeroed above
-    cc.NK = cc_nk(h->Kc); cc.NG = 8 * cc.NK; cc.NHEAD = (R + 15) / 16;
-    cc.hp = ca.hp;
-    if (env_item("MQ_DIAG", "coma_trace") &&
-        (rc = h->chain_trace.alloc(16 * 8, "hipMalloc(&h->chain_trace, 16 * 8 * sizeof(unsigned long long))")))
-      return rc;
-    cc.trace = h->chain_trace;
-    cc.fault_wg = env_int("MQ_DIAG", "coma_fault", -1);   // test hook: a workgroup that stops flagging
-    // cnorm: [0, 2 G) the norm granules, [512, 512 + G) flagA, [768, 768 + NHEAD) flagB; no stale step tags
-    cc.flagA = (unsigned*)(h->cnorm + 512);
-    cc.flagB = (unsigned*)(h->cnorm + 768);
-    MQ_HIP(hipMemsetAsync(h->cnorm, 0, 1024 * sizeof(float), s));
-    const size_t lds = cc_lds_bytes(A);
-    MQ_LDS(coma_chain_kernel, lds);
-    if (!h->chain_attr) {
-      MQ_HIP(hipFuncSetAttribute((const void*)coma_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      h->chain_attr = true;
-    }
-    // the chain updates the critic in place: keep the pre-train version, restored below if a hand-off times out
-    MQ_HIP(hipMemcpyAsync(h->Pbak, h->critic, (size_t)h->Pc * sizeof(float), hipMemcpyDeviceToDevice, s));
-    MQ_HIP(hipMemcpyAsync(h->Pbak + h->Pc, h->csq, (size_t)h->Pc * sizeof(float), hipMemcpyDeviceToDevice, s));
-    // A plain launch: the grid (cc_ok: at most one 512-thread workgroup per CU, NG <= the CU count) is resident
-    // by its size alone, which is all a cooperative launch would add a check for (MI355X_MICROARCH.md "Residency
-    // and cooperative launch": plain and cooperative launches give the same residency). Nothing else on the device
-    // waits on the chain, so a workgroup that starts late only delays it; every spin is bounded. The cooperative
-    // launch also cost 15-19 us of host time per train and, under rocprofv3, its dedicated HIP queue crashed the
-    // runtime's exit-time teardown (round 4: profiles/r04a_cfg5_rocprof_exit_crash.txt)
-    hipLaunchKernelGGL(coma_chain_kernel, dim3(cc.NG), dim3(CC_THREADS), lds, s, cc);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-      chained = true;
-      // failure semantics: after a timed-out hand-off the critic (params, square_avg) is put back to its pre-train
-      // version before the actor's apply (coma_chain_restore_kernel below) and the actor's apply is skipped (its
-      // halt word), so the learner state is this train()'s starting state and COMALearner.train raises
-      if (h->chain_trace) {   // debug: per-phase spans of workgroup 0 (100 MHz clock), averaged over <= 16 steps
-        unsigned long long hb[16 * 8];
-        MQ_HIP(hipMemcpyAsync(hb, h->chain_trace, sizeof(hb), hipMemcpyDeviceToHost, s));
-        MQ_HIP(hipStreamSynchronize(s));
-        double acc[8] = {0};
-        for (int i = 1; i < 15; ++i)
-          for (int k = 0; k < 8; ++k) acc[k] += 10.0 * (double)((k < 7 ? hb[i * 8 + k + 1] : hb[(i + 1) * 8]) - hb[i * 8 + k]);
-        std::fprintf(stderr, "coma_chain ns/step: A %.0f bar1 %.0f B %.0f bar2 %.0f C %.0f bar3 %.0f D %.0f next %.0f\n",
-                     acc[0] / 14, acc[1] / 14, acc[2] / 14, acc[3] / 14, acc[4] / 14, acc[5] / 14, acc[6] / 14, acc[7] / 14);
-      }
-    } else {   // the launch was refused: the three-launch path, from now on
-      h->chain_env = false;
-    }
-    // Launched after the chain on a low-priority stream, so the chain's workgroups are normally dispatched first.
-    // That order is a heuristic across hardware queues, not a guarantee: if actor workgroups take CUs first, the
-    // chain's late workgroups start when they finish (the actor never waits on the chain), well inside the chain's
-    // spin bound (CC_SPIN_LIMIT polls, orders of magnitude longer than the actor unroll); a timeout would still be
-    // loud and leave the learner state unchanged (restore above)
-    if (chained && try_overlap) {
-      MQ_HIP(hipStreamWaitEvent(ah->side, ah->ev_fork, 0));
-      if ((rc = agent_forward(ah->side)) != MQ_OK) return rc;
-      MQ_HIP(hipEventRecord(ah->ev_join, ah->side));
-      actor_side = true;
-    }
-  }
-  int live = 0;
-  for (int t = T - 1; t >= 0 && !chained; --t) {
-    // live steps before t: exact in data-parallel mode, else assumed none was skipped (the kernels correct it)
-    const int Lexp = dp ? live : T - 1 - t;
-    hipLaunchKernelGGL(coma_l1_kernel, dim3(ca.KS, CH / 16, (R + kL1Rows - 1) / kL1Rows), dim3(256), lds_l1, s, ca, t,
-                       Lexp);
-    hipLaunchKernelGGL(coma_head_kernel, dim3(ca.nhead), dim3(kHeadThreads), lds_head, s, ca, t, Lexp);
-    hipLaunchKernelGGL(coma_wgrad_kernel, dim3(ca.nwgrad), dim3(256), 0, s, ca, t);
-    if (dp && h->dp_msum[t] > 0.0f) {   // sum the step's unnormalised gradient, then its norm from the sum
-      ++live;
-      MQ_HIP(hipGetLastError());
-      rc = mc_allreduce(h, h->cgrad, h->Pc, s);
-      if (rc) return rc;
-      hipLaunchKernelGGL(sumsq_kernel, dim3(ca.nwgrad), dim3(256), 0, s, (const float*)h->cgrad, h->Pc, h->cnorm);
-    }
-  }
-  MQ_HIP(hipGetLastError());
-  if (!chained)
-    hipLaunchKernelGGL(coma_capply_kernel, dim3((int)std::min<int64_t>((h->Pc + 255) / 256, 512)), dim3(256), 0, s,
-                       ca);
-  MQ_HIP(hipGetLastError());
-  if (dp) {   // per-step critic stat sums; the replicated fields (mask sum, norm, live flag) come from rank 0
-    if (h->dp_rank != 0) hipLaunchKernelGGL(coma_dp_crec_kernel, dim3((T + 255) / 256), dim3(256), 0, s, h->crec, T);
-    MQ_HIP(hipGetLastError());
-    rc = mc_allreduce_ws(h, h->crec, 8LL * T, s);
-    if (rc) return rc;
-  }
-
-  if (h->timing) MQ_HIP(hipEventRecord(h->ev[2], s));
-  // ---- actor: the agent unroll over t < T (coma_learner.py:52-57), online net only (launched above)
-  if (actor_side) MQ_HIP(hipStreamWaitEvent(s, ah->ev_join, 0));
-  else if ((rc = agent_forward(s)) != MQ_OK) return rc;
-  // policy, baseline, advantage, loss sums and dLogits (coma_learner.py:59-77, basic_controller.py:53-73)
-  const int npol = (int)((RT + 3) / 4);
-  const float eps = epsilon, omeps = (float)(1.0 - (double)epsilon);
-  hipLaunchKernelGGL(coma_policy_kernel, dim3(npol), dim3(256), 0, s, d, rpa, (const float*)w.Q,
-                     (const float*)h->qvals, R, qv_r0, eps, omeps, (int)(c.mask_before_softmax != 0), h->Ap, h->dL,
-                     h->pi, h->ppart);
-  MQ_HIP(hipGetLastError());
-  // BPTT with the dense output gradient, the weight gradients and their reduction
-  int nnorm;
-  if ((rc = actor_backward(ah, d, rpa, Pa, L, w, RT, h->dL, h->Ap, h->slab_fc2, h->ppart, npol, h->red_tmp,
-                           h->norm_part, h->agrad, h->Pa, s, &nnorm)))
+  // exchange mode (an all-reduce and no shard): the critic steps are summed over the ranks. MQ_PLAN coma_overlap=0,
+  // read per train(): the actor's agent unroll stays on the caller's stream
+  const ComaMode mode{h->dp_fn != nullptr && !repl, repl, h->timing, h->chain_env, plan_int("coma_overlap", 1) != 0,
+                      h->shard_lo, h->shard_hi};
+  const ComaPlan pl = coma_plan(h->cfg, batch->batch_size, batch->t_len, h->num_cu, mode);
+  if (pl.refused) return set_err(MQ_ERR_ARG, pl.refused);
+  ComaStep st = make_coma_step(h, batch, pl, mode, epsilon, (hipStream_t)stream);
+  if ((rc = st.targets()) || (rc = st.critic_chain()) || (rc = st.critic_steps()) || (rc = st.actor()) ||
+      (rc = st.exchange()) || (rc = st.apply_and_stats()))
     return rc;
-  if (repl && chained) {   // the chain's error word rides in the agent sums' spare slot 7 (0 on success)
-    hipLaunchKernelGGL(coma_halt_to_sum_kernel, dim3(1), dim3(64), 0, s, (const int*)(h->cstate + 3),
-                       h->agrad + h->Pa + 7);
-    MQ_HIP(hipGetLastError());
-  }
-  if (dp || repl) {   // the agent gradient + loss / mask sums, then the norm partials of the summed gradient
-    rc = mc_allreduce(h, h->agrad, h->Pa + MQ_NSUMS, s);
-    if (rc) return rc;
-    if (repl && chained) {   // any rank's chain failure halts every rank: all roll back, skip the apply and raise
-      hipLaunchKernelGGL(coma_sum_to_halt_kernel, dim3(1), dim3(64), 0, s, (const float*)(h->agrad + h->Pa + 7),
-                         h->cstate + 3);
-      MQ_HIP(hipGetLastError());
-    }
-    nnorm = 256;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(nnorm), dim3(256), 0, s, (const float*)h->agrad, h->Pa, h->norm_part);
-    MQ_HIP(hipGetLastError());
-  }
-  if (chained) {   // a timed-out chain (on any rank, when replicated): the critic back to its pre-train version
-    hipLaunchKernelGGL(coma_chain_restore_kernel, dim3(64), dim3(256), 0, s, (const int*)h->cstate,
-                       (const float*)h->Pbak, h->critic, h->csq, h->Pc);
-    MQ_HIP(hipGetLastError());
-  }
-  {
-    OptHP hp{c.lr, c.optim_alpha, c.optim_eps, c.grad_norm_clip, 1};
-    const int blocks = (int)std::min<int64_t>((h->Pa + 255) / 256, 1024);
-    hipLaunchKernelGGL(apply_kernel, dim3(blocks), dim3(256), 0, s, h->agent, h->agrad, h->asq, h->Pa,
-                       (const float*)h->norm_part, nnorm, hp, h->stats + 8,
-                       chained ? (const int*)(h->cstate + 3) : (const int*)nullptr);   // no actor step after a failure
-    MQ_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(coma_stats_kernel, dim3(1), dim3(64), 0, s, (const float*)h->crec, T,
-                     (const int*)h->cstate, h->stats);
-  MQ_HIP(hipGetLastError());
-  if (h->timing) MQ_HIP(hipEventRecord(h->ev[3], s));
-  h->last_path = chained ? 1 : 0;
-  h->last_T = T;
-  h->last_R = d.R;   // the rows of pi (the actor's); qvals / targets keep the critic's R rows
-  h->last_Rc = R;
+  h->last_path = st.chained ? 1 : 0;
+  h->last_T = pl.T;
+  h->last_R = pl.actor_R;   // the rows of pi (the actor's); qvals / targets keep the critic's R rows
+  h->last_Rc = pl.R;
   return MQ_OK;
 }
 

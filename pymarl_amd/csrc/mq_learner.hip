@@ -29,8 +29,11 @@
 // The host side by file: host_util.hpp (errors, HIP / LDS checks, device-buffer owner, workspace table),
 // learner_layout.hpp (parameter layout and workspace sizes from the config), step_plan.hpp and reduce_plan.hpp (what a
 // step launches, decided without a HIP call), learner_handle.hpp (mq_handle, batch checks), step_launch.hpp (the
-// launches), optim_host.hpp (Adam's host side), coma_host.hpp (the COMA learner), a2c_host.hpp (the actor-critic learner, with
-// a2c_plan.hpp and a2c_kernels.hpp). This file holds the C ABI.
+// launches), optim_host.hpp (Adam's host side, and launch_reduce: the two-pass reduction's launcher outside Step),
+// actor_plan.hpp (what the policy-gradient actor launches, for the three learners below), coma_plan.hpp (what a COMA
+// step launches, decided without a HIP call) and coma_host.hpp (the COMA learner: its handle, the shared actor, the
+// step's phases), a2c_host.hpp (the actor-critic learner, with a2c_plan.hpp and a2c_kernels.hpp), ppo_host.hpp (its
+// PPO step). This file holds the C ABI.
 #include <algorithm>
 #include <cstring>
 #include <memory>

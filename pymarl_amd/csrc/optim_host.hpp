@@ -1,5 +1,6 @@
 // The optimisers' host side: Adam's argument checks and per-step scalars (apply_adam_kernel), and the grid of the
-// float4 element-wise kernels (apply_adam_kernel, soft_update_kernel).
+// float4 element-wise kernels (apply_adam_kernel, soft_update_kernel), and the launcher of the two-pass slab reduction
+// for the learners whose norm_part has a fixed size (launch_reduce).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -9,6 +10,7 @@
 
 #include "host_util.hpp"
 #include "optim_kernels.hpp"
+#include "reduce_plan.hpp"
 
 namespace {
 
@@ -57,6 +59,19 @@ int vec4_blocks(std::initializer_list<const float*> ptrs, int64_t n) {
   for (const float* p : ptrs) same = same && ((uintptr_t)p & 15) == ((uintptr_t)*ptrs.begin() & 15);
   const int64_t items = same ? n / 4 + 6 : n;
   return (int)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, 1024));
+}
+
+// The two-pass reduction of rb's regions (red_pass1_kernel, red_pass2_kernel) for `who` ("agent" / "critic"), checked
+// against the region table and the norm-partial cap before the first launch; *nnorm = the partials left in norm_part.
+int launch_reduce(const RedBuilder& rb, float* norm_part, const char* who, hipStream_t s, int* nnorm) {
+  if (!rb.ok) return set_err(MQ_ERR_STATE, std::string(who) + ": more reduction regions than the plan holds");
+  if (rb.b2 > kNormPartMax) return set_err(MQ_ERR_ARG, std::string(who) + " too large for the norm partial buffer");
+  hipLaunchKernelGGL(red_pass1_kernel, dim3(rb.b1), dim3(256), 0, s, rb.pl);
+  MQ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(red_pass2_kernel, dim3(rb.b2), dim3(256), 0, s, rb.pl, norm_part);
+  MQ_HIP(hipGetLastError());
+  *nnorm = rb.b2;
+  return MQ_OK;
 }
 
 }  // namespace

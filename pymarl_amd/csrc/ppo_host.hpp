@@ -15,30 +15,18 @@ int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStr
   const int B = batch->batch_size, Tp = batch->t_len, T = Tp - 1, R = B * n;
   const Rep rp = make_rep(batch);
   const ADims cd = ma_dims(c, B, Tp, batch->t_stride);
-  ma_plan pl = a2c_plan(c, B, Tp, h->rew_state != nullptr, h->adam);
-  const int64_t RT = (int64_t)T * R, RTp = (int64_t)Tp * R;
-  // the plan's slabs against what ma_create allocated (max_batch / max_seq bound both, old_lp and ratio included)
-  if (pl.ns_cw1 > h->ns_max || pl.ns_cw2 > h->ns_max || pl.dv_blocks > h->ndv_max || pl.ns_aw2 > kNsplitMax)
-    return set_err(MQ_ERR_STATE, "actor-critic plan exceeds the workspace");
-  const size_t lds_ns = a2c_nstep_lds_bytes(Tp, n);
-  if (lds_ns > kA2cNstepLdsMax) return set_err(MQ_ERR_ARG, "episode too long for the LDS n-step return pass");
-  const float lo = (float)(1.0 - (double)h->pp.eps_clip), hi = (float)(1.0 + (double)h->pp.eps_clip);
+  ma_plan pl;
+  ActorPlan ap;
   int rc, hoisted = 0;
+  if ((rc = ma_step_plan(h, B, Tp, &pl, &ap))) return rc;
+  const int64_t RT = (int64_t)T * R, RTp = (int64_t)Tp * R;
+  const float lo = (float)(1.0 - (double)h->pp.eps_clip), hi = (float)(1.0 + (double)h->pp.eps_clip);
 
   // ---- once per train(): X, the target critic's fc1 / fc2 / V head over t <= T
   hipLaunchKernelGGL(a2c_xin_kernel, dim3((unsigned)((RTp + 3) / 4)), dim3(256), 0, s, cd, rp, h->X, 0, RTp);
   MQ_HIP(hipGetLastError());
   const float *tc = h->tcritic, *oc = h->critic;
-  auto forward = [&](const float* P, float* H1, float* H2, int64_t rows) -> int {
-    const CLinProbT<64> l1 =
-        CLinProbT<64>{h->X, h->Kp, P + h->coff[MA_P_FC1_W], P + h->coff[MA_P_FC1_B], H1, rows, Hc, h->K, 1}.with_vec();
-    MQ_HIP(launch_gemm(l1, (int)rows, Hc, 1, s));
-    const CLinProbT<64> l2 =
-        CLinProbT<64>{H1, Hc, P + h->coff[MA_P_FC2_W], P + h->coff[MA_P_FC2_B], H2, rows, Hc, Hc, 1}.with_vec();
-    MQ_HIP(launch_gemm(l2, (int)rows, Hc, 1, s));
-    return MQ_OK;
-  };
-  if ((rc = forward(tc, h->H1t, h->H2t, RTp))) return rc;
+  if ((rc = ma_critic_l12(tc, h->coff, cd, h->X, h->H1t, h->H2t, RTp, s))) return rc;
   hipLaunchKernelGGL(a2c_vhead_kernel, dim3((unsigned)((RTp + 3) / 4)), dim3(256), 0, s, (const float*)h->H2t,
                      (const float*)nullptr, tc, oc, h->coff[MA_P_FC3_W], h->coff[MA_P_FC3_B], Hc, RTp, (int64_t)0, h->Vt,
                      (float*)nullptr, R, n, 0);
@@ -46,17 +34,8 @@ int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStr
   hoisted += 4;
   const Dims d = mq::make_dims(ah->cfg, B, T, batch->t_stride);   // d.Tp = T: d.RT() = T R
   // ---- once: the rewards standardised (the running statistics merge the batch once), the n-step returns
-  if (h->rew_state) {
-    MQ_HIP(hipMemcpyAsync(h->rbak, h->rew_state, 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    const Dims dr = mq::make_dims(ah->cfg, B, Tp, batch->t_stride);
-    hipLaunchKernelGGL(reward_norm_kernel, dim3(1), dim3(RN_THREADS), 0, s, dr, rp, h->rew_state, h->RS);
-    MQ_HIP(hipGetLastError());
-    hoisted += 2;
-  }
-  hipLaunchKernelGGL(a2c_nstep_kernel, dim3(B), dim3(256), lds_ns, s, cd, rp, (const float*)h->Vt,
-                     (const float*)(h->rew_state ? h->RS : nullptr), (const float*)h->gpow, (int)c.q_nstep,
-                     (int)(c.add_value_last_step != 0), h->ret);
-  MQ_HIP(hipGetLastError());
+  if ((rc = ma_returns(h, cd, rp, pl, s))) return rc;
+  hoisted += h->rew_state ? 2 : 0;
   // ---- once: both gradient buffers as the caller left them (an empty batch puts them back after every epoch)
   const int64_t na = h->Pa + MQ_NSUMS, nc = h->Pc + MA_NTAIL;
   MQ_HIP(hipMemcpyAsync(h->gbak, h->agrad, (size_t)na * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -66,11 +45,10 @@ int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStr
   const Lay L = make_lay(ah);
   Work w = ah->w;
   w.dHo = h->dHo;
-  const float* Pa = h->agent;
   const int mbs = (int)(c.mask_before_softmax != 0);
   for (int k = 0; k < E; ++k) {
     // ---- critic: V of the current parameters over t < T, td against the fixed returns
-    if ((rc = forward(oc, h->H1o, h->H2o, RT))) return rc;
+    if ((rc = ma_critic_l12(oc, h->coff, cd, h->X, h->H1o, h->H2o, RT, s))) return rc;
     hipLaunchKernelGGL(a2c_vhead_kernel, dim3((unsigned)((RT + 3) / 4)), dim3(256), 0, s, (const float*)nullptr,
                        (const float*)h->H2o, tc, oc, h->coff[MA_P_FC3_W], h->coff[MA_P_FC3_B], Hc, (int64_t)0, RT,
                        (float*)nullptr, h->Vo, R, n, 0);
@@ -80,7 +58,7 @@ int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStr
                        h->cpart);
     MQ_HIP(hipGetLastError());
     // ---- actor forward and the clipped surrogate (epoch 0 writes the old log-probabilities)
-    if ((rc = actor_forward(ah, d, rp, Pa, L, w, RT, s))) return rc;
+    if ((rc = actor_forward(h, ap, d, rp, L, w, RT, s))) return rc;
     if (k == 0)
       hipLaunchKernelGGL(ppo_policy_kernel<true>, dim3(pl.policy_blocks), dim3(256), 0, s, d, rp, (const float*)w.Q,
                          (const float*)h->td, c.entropy_coef, lo, hi, mbs, h->Ap, h->old_lp, h->ratio, h->dL, h->pi,
@@ -93,8 +71,7 @@ int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStr
     // ---- both backwards, then both applies (Adam step number adam_step + k), then the epoch's stats row
     int nnorm_c, nnorm_a;
     if ((rc = ma_critic_dw(h, pl, RT, s)) || (rc = ma_critic_reduce(h, pl, s, &nnorm_c)) ||
-        (rc = actor_backward(ah, d, rp, Pa, L, w, RT, h->dL, h->Ap, h->slab_fc2, h->ppart, pl.policy_blocks, h->red_tmp,
-                             h->norm_part, h->agrad, h->Pa, s, &nnorm_a)) ||
+        (rc = actor_backward(h, ap, d, rp, L, w, RT, pl.policy_blocks, s, &nnorm_a)) ||
         (rc = ma_gate_apply(h, nnorm_c, nnorm_a, adam_step + k, s)))
       return rc;
     hipLaunchKernelGGL(ppo_stats_kernel, dim3(1), dim3(64), 0, s, (const float*)h->stats,

@@ -1,11 +1,15 @@
 // The slab reductions of one train step (optim_kernels.hpp red_pass1_kernel / red_pass2_kernel) as a plan: a pure
 // function of the step's plan, its shapes, the parameter layout and the workspace pointers. No HIP call: the launches
-// are Step::reduce's (step_launch.hpp), and tests/host/ws_probe.cpp reads off it what a step asks of red_tmp and
-// norm_part.
+// are Step::reduce's (step_launch.hpp) and launch_reduce's (optim_host.hpp), and tests/host/ws_probe.cpp reads off it
+// what a step asks of red_tmp and norm_part.
 #pragma once
 #include "learner_layout.hpp"
 
 namespace mq {
+
+// Norm partials (pass 2's blocks) a norm_part buffer of fixed size holds: the COMA and actor-critic workspaces'
+// tables and launch_reduce's check (optim_host.hpp) share it.
+constexpr int kNormPartMax = 4096;
 
 // Regions in gradient order, then the loss sums (not part of the norm).
 struct RedBuilder {
@@ -13,11 +17,13 @@ struct RedBuilder {
   int b1 = 0, b2 = 0;   // blocks of pass 1 / pass 2 (pass 2 writes one norm_part float per block)
   float* tmp;
   bool mix_direct = false;   // plan_reduce: dW_hyper's slabs go straight to pass 2
+  bool ok = true;            // cleared by a region past kRedMaxRegions: nothing was written for it, launch nothing
   explicit RedBuilder(float* t) : tmp(t) {}
   // returns true when the region is summed by pass 2 straight from its slabs (no pass-1 blocks read them)
   bool add(const float* src, int nslab, int64_t len, float* dst, bool sq, int64_t pitch = 0, bool direct_ok = false,
            int perm = 0) {
     if (len <= 0 || nslab <= 0) return false;
+    if (pl.nr >= kRedMaxRegions) return ok = false;
     RedRegion& R = pl.r[pl.nr++];
     R.src = src; R.dst = dst; R.len = len; R.pitch = pitch > 0 ? pitch : len; R.nslab = nslab; R.sq = sq ? 1 : 0;
     R.perm = perm;

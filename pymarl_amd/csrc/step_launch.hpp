@@ -360,6 +360,7 @@ int Step::bptt(const StepPlan& p) {
 // dW_hyper's tiles rode in the BPTT's grid.
 int Step::reduce(const StepPlan& p) {
   const RedBuilder rb = plan_reduce(p, d, *h, w, h->grad);
+  if (!rb.ok) return set_err(MQ_ERR_STATE, "step: more reduction regions than the plan holds");
   // pass-1 blocks would read slabs the dW_hyper blocks of the same grid still write
   if (p.dwh_in_red1 && !rb.mix_direct)
     return set_err(MQ_ERR_STATE, "dW_hyper fused with reduction pass 1 needs a direct slab region");

@@ -5,7 +5,8 @@
 //            unfused_fwd, unfused_bwd, row_tiles=0|1, hyp_in_fwd=0|1, dwh_in_bwd=0|1, dwh_split=<n>, fwd_pair=0|1,
 //            bwd_lean=0|1, pair_hyp_epi, mix_generic, lambda_path=1 (the TD(lambda) passes of the mixer tail even at
 //            mq_config.td_lambda = 0), ffn_dp2_blocks=<n> (feed-forward agent: ffn_dp2_kernel's workgroup cap);
-//            COMA's where they are used (coma_host.hpp): coma_chain=0 (mc_create), coma_overlap=0 (per train())
+//            COMA's are read in coma_host.hpp and enter coma_plan through its ComaMode (coma_plan.hpp calls no
+//            getenv): coma_chain=0 (mc_create), coma_overlap=0 (per train())
 //   MQ_DIAG  diagnostics and test hooks, read per train(): pair_stamp=<file> (the row-pair forward's s_memtime
 //            stamps), bwd_stamp=<file> (the fused BPTT's), hyp_sched=<hex> (the pair forward's in-loop hypernet tile
 //            schedule), coma_trace (the COMA chain's phase times), coma_fault=<workgroup> (a chain workgroup that
