@@ -299,75 +299,58 @@ def require_gpu(tensor_or_device):
                       "fallback — call .cuda() on the learner/MAC and keep the replay on the GPU")
 
 
-class Handle:
-    """RAII owner of an mq_handle."""
+class _Owner:
+    """RAII owner of a library handle: <PREFIX>_create on construction, <PREFIX>_destroy on collection, and one list
+    of parameter offsets per entry of OFFSETS (attribute name, parameter count), read with <PREFIX>_param_offsets."""
+    PREFIX, OFFSETS = None, ()
 
-    def __init__(self, cfg: MQConfig):
+    def __init__(self, cfg):
         self.lib = load()
         h = ctypes.c_void_p()
-        check(self.lib.mq_create(ctypes.byref(cfg), ctypes.byref(h)))
+        check(self._fn("create")(ctypes.byref(cfg), ctypes.byref(h)))
         self.h = h
         self.cfg = cfg
-        offs = (ctypes.c_int64 * (P_COUNT + 1))()
-        check(self.lib.mq_param_offsets(self.h, offs))
-        self.offsets = list(offs)
+        offs = [(ctypes.c_int64 * (count + 1))() for _, count in self.OFFSETS]
+        check(self._fn("param_offsets")(self.h, *offs))
+        for (name, _), o in zip(self.OFFSETS, offs):
+            setattr(self, name, list(o))
+
+    def _fn(self, name):
+        return getattr(self.lib, "{}_{}".format(self.PREFIX, name))
 
     def __del__(self):
         try:
             if getattr(self, "h", None) and self.h.value:
-                self.lib.mq_destroy(self.h)
+                self._fn("destroy")(self.h)
                 self.h = ctypes.c_void_p()
         except Exception:
             pass
+
+    def copy_intermediate(self, which, device):
+        """<PREFIX>_copy_intermediate's two calls (the size, then the copy on the current stream): array `which` of
+        the last step as a flat float32 tensor on `device`."""
+        import torch
+        cnt = ctypes.c_int64()
+        check(self._fn("copy_intermediate")(self.h, which, None, ctypes.byref(cnt), None))
+        out = torch.empty(cnt.value, dtype=torch.float32, device=device)
+        check(self._fn("copy_intermediate")(self.h, which, ptr(out), ctypes.byref(cnt), stream_ptr()))
+        return out
+
+
+class Handle(_Owner):
+    """Owner of an mq_handle (include/mq_learner.h)."""
+    PREFIX, OFFSETS = "mq", (("offsets", P_COUNT),)
 
     @property
     def n_params(self):
         return self.offsets[-1]
 
 
-class ComaHandle:
-    """RAII owner of an mc_handle (include/mc_coma.h)."""
-
-    def __init__(self, cfg: MCConfig):
-        self.lib = load()
-        h = ctypes.c_void_p()
-        check(self.lib.mc_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self.h = h
-        self.cfg = cfg
-        ao = (ctypes.c_int64 * (P_COUNT + 1))()
-        co = (ctypes.c_int64 * (MC_P_COUNT + 1))()
-        check(self.lib.mc_param_offsets(self.h, ao, co))
-        self.agent_offsets = list(ao)
-        self.critic_offsets = list(co)
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None) and self.h.value:
-                self.lib.mc_destroy(self.h)
-                self.h = ctypes.c_void_p()
-        except Exception:
-            pass
+class ComaHandle(_Owner):
+    """Owner of an mc_handle (include/mc_coma.h)."""
+    PREFIX, OFFSETS = "mc", (("agent_offsets", P_COUNT), ("critic_offsets", MC_P_COUNT))
 
 
-class A2CHandle:
-    """RAII owner of an ma_handle (include/ma_a2c.h)."""
-
-    def __init__(self, cfg: MAConfig):
-        self.lib = load()
-        h = ctypes.c_void_p()
-        check(self.lib.ma_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self.h = h
-        self.cfg = cfg
-        ao = (ctypes.c_int64 * (P_COUNT + 1))()
-        co = (ctypes.c_int64 * (MA_P_COUNT + 1))()
-        check(self.lib.ma_param_offsets(self.h, ao, co))
-        self.agent_offsets = list(ao)
-        self.critic_offsets = list(co)
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None) and self.h.value:
-                self.lib.ma_destroy(self.h)
-                self.h = ctypes.c_void_p()
-        except Exception:
-            pass
+class A2CHandle(_Owner):
+    """Owner of an ma_handle (include/ma_a2c.h)."""
+    PREFIX, OFFSETS = "ma", (("agent_offsets", P_COUNT), ("critic_offsets", MA_P_COUNT))

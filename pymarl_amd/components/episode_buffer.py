@@ -25,6 +25,8 @@ from types import SimpleNamespace as SN
 import numpy as np
 import torch as th
 
+from .. import _lib
+
 
 def _prod(shape):
     return reduce(lambda a, b: a * b, shape, 1)
@@ -348,6 +350,94 @@ class PrioritizedBatch(SampledBatch):
                          "learner writes the priorities back into that buffer".format(self.device, device))
 
 
+def is_per_batch(batch):
+    """True for a PrioritizedReplayBuffer sample: train() runs it as a prioritized-replay step."""
+    return isinstance(batch, PrioritizedBatch)
+
+
+_FIELDS = [("obs", th.float32), ("state", th.float32), ("actions", th.int64), ("avail_actions", th.int32),
+           ("reward", th.float32), ("terminated", th.uint8), ("filled", th.int64)]
+
+
+def _field_view(t, dtype):
+    """(tensor usable by the kernels, t_stride): [B][T][...] with trailing dims contiguous and the right dtype."""
+    if t.dtype != dtype:
+        t = t.to(dtype)
+    inner = 1
+    for s in t.shape[2:]:
+        inner *= s
+    ok = t.stride(1) == inner and t.stride(0) % max(1, inner) == 0 and t[0, 0].is_contiguous()
+    if not ok:
+        t = t.contiguous()
+    return t, t.stride(0) // max(1, inner)
+
+
+def replay_view(batch, avail_bits=True):
+    """MQReplay for an EpisodeBatch (episode-major storage) or a SampledBatch (storage + device ids).
+    Returns (struct, keepalive) — keep the second alive until the kernels that read it have been queued.
+    avail_bits: hand the kernels the buffer's avail bitmask (ReplayBuffer.avail_bits_current: rebuilt first if the
+    storage was written behind its back), else they read the int32 avail_actions rows."""
+    keep = []
+    rep = _lib.MQReplay()
+    if is_replay_view(batch):
+        src = batch.source.data.transition_data
+        tstride = batch.source.max_seq_length
+        if is_per_batch(batch):
+            # prioritized replay: the ids were written by the sampler kernel and exist on the device only
+            ids = batch.ep_ids
+            keep.append(ids)
+            rep.ep_ids = ids.data_ptr()
+            rep.ep_ids_host = None
+        elif len(batch.ep_ids_np) <= _lib.INLINE_IDS:
+            # ids travel in the kernel arguments: no host-to-device copy on the step's stream
+            host = np.ascontiguousarray(batch.ep_ids_np, dtype=np.int64)
+            keep.append(host)
+            rep.ep_ids_host = host.ctypes.data
+            rep.ep_ids = None
+        else:
+            ids = batch.ep_ids
+            keep.append(ids)
+            rep.ep_ids = ids.data_ptr()
+        rep.n_episodes = batch.source.batch_size
+        rep.t_len = batch.t_len
+        tensors = {}
+        for k, dt in _FIELDS:
+            if k not in src:
+                continue
+            t = src[k]
+            if t.dtype != dt or not t.is_contiguous():
+                raise _lib.MQError("replay field {} must be a contiguous {} tensor".format(k, dt))
+            tensors[k] = t
+        cur = getattr(batch.source, "avail_bits_current", None)
+        bits = cur() if (avail_bits and cur is not None) else None
+        if bits is not None:
+            keep.append(bits)
+            rep.avail_bits = bits.data_ptr()
+    else:
+        src = batch.data.transition_data
+        tensors, strides = {}, set()
+        for k, dt in _FIELDS:
+            if k not in src:
+                continue
+            t, ts = _field_view(src[k], dt)
+            tensors[k] = t
+            strides.add(ts)
+        if len(strides) != 1:
+            tensors = {k: v.contiguous() for k, v in tensors.items()}
+            strides = {batch.max_seq_length}
+        tstride = strides.pop()
+        rep.ep_ids = None
+        rep.n_episodes = batch.batch_size
+        rep.t_len = batch.max_seq_length
+    for k, t in tensors.items():
+        keep.append(t)
+        setattr(rep, k, t.data_ptr())
+    _lib.require_gpu(tensors["obs"])
+    rep.batch_size = batch.batch_size
+    rep.t_stride = int(tstride)
+    return rep, keep
+
+
 class _LazyGather(dict):
     def __init__(self, batch, transition):
         super().__init__()
@@ -529,7 +619,6 @@ class PrioritizedReplayBuffer(ReplayBuffer):
     def sample(self, batch_size, u=None):
         """`batch_size` draws (duplicates allowed) as a PrioritizedBatch. u: optional [batch_size] numbers in [0, 1),
         one per stratum, in place of the generator's (tests)."""
-        from .. import _lib
         assert self.can_sample(batch_size)
         _lib.require_gpu(self.prio)
         dev = self.prio.device

@@ -18,6 +18,7 @@ import torch as th
 
 from .. import _lib
 from ..components.action_selectors import REGISTRY as action_REGISTRY
+from ..components.episode_buffer import replay_view
 from ..modules.agents import REGISTRY as agent_REGISTRY
 from ..modules.agents.rnn_agent import hidden_dim, use_rnn_config
 
@@ -62,7 +63,6 @@ class BasicMAC:
     def _forward(self, ep_batch, t, test_mode=False):
         if self.agent_output_type not in ("q", "pi_logits"):
             raise NotImplementedError("agent_output_type {!r}".format(self.agent_output_type))
-        from ..learners.q_learner import replay_view
         dev = self.agent.fc1.weight.device
         _lib.require_gpu(self.agent.fc1.weight)
         t_run = t

@@ -10,9 +10,9 @@ buffers. There is no CPU path. One synchronisation per train(): the stats read-b
 live transition (an empty one changes nothing and counts nothing).
 
 Keys: `lr` (both optimisers), `optimizer` (absent or `adam`: torch.optim.Adam with torch's defaults, read through
-q_learner.optimizer_config; `rmsprop`: the reference's RMSprop), `grad_norm_clip`, `target_update_interval_or_tau`
-(q_learner.target_update_config's rules counted in critic training steps; absent: a hard update every
-`target_update_interval`, default 200, critic training steps), `standardise_rewards` (q_learner.reward_norm_config),
+keys.optimizer_config; `rmsprop`: the reference's RMSprop), `grad_norm_clip`, `target_update_interval_or_tau`
+(keys.target_update_config's rules counted in critic training steps; absent: a hard update every
+`target_update_interval`, default 200, critic training steps), `standardise_rewards` (keys.reward_norm_config),
 `hidden_dim` (the critic's width, 64 or 128), `mask_before_softmax` (default True). Refused with ValueError:
 `use_rnn: False`, `learner_dp`, `standardise_returns: True`, `obs_individual_obs: True`, a critic_type other than the
 two, and a PrioritizedReplayBuffer batch.
@@ -21,7 +21,6 @@ from __future__ import annotations
 
 import copy
 import ctypes
-import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -29,12 +28,12 @@ import torch as th
 from torch.optim import Adam, RMSprop
 
 from .. import _lib
-from ..components.episode_buffer import is_replay_view
-from ..modules.agents.rnn_agent import use_rnn_config
+from ..components.episode_buffer import is_per_batch, is_replay_view, replay_view
+from ..modules.agents.rnn_agent import obs_dim, use_rnn_config
 from ..modules.critics import REGISTRY as critic_REGISTRY
-from ..modules.flat import pack, rebind
-from .q_learner import (REW_MS_INIT, is_per_batch, optimizer_config, replay_view, reward_norm_config,
-                        target_update_config)
+from ..modules.flat import link, load_state, pack, rebind, state_buffers, state_dict_own_steps, to_current_device
+from .keys import (REW_MS_INIT, hard_target_update, load_rew_ms, optimizer_config, reward_norm_config, reward_stats,
+                   save_rew_ms, target_update_config)
 
 CRITIC_TYPES = ("cv_critic", "ac_critic")
 A2C_STATS = list(_lib.A2C_STATS)
@@ -87,8 +86,7 @@ def make_a2c_config(args, ac, input_dim, critic, max_batch, max_seq, gpow):
     cfg = _lib.MAConfig()
     cfg.n_agents = args.n_agents
     cfg.n_actions = args.n_actions
-    cfg.obs_dim = int(input_dim - (args.n_actions if args.obs_last_action else 0) -
-                      (args.n_agents if args.obs_agent_id else 0))
+    cfg.obs_dim = obs_dim(args, input_dim)
     cfg.state_dim = critic.state_dim
     cfg.rnn_hidden_dim = 64
     cfg.critic_hidden = critic.hidden_dim
@@ -169,18 +167,7 @@ class ActorCriticLearner:
         self._step_t = th.tensor(float(self._opt_steps))   # one counter shared by every parameter of both optimisers
         for params, grad, sq, m, opt in ((self.agent_params, self._agrad, self._asq, self._am, self.agent_optimiser),
                                          (self.critic_params, self._cgrad, self._csq, self._cm, self.critic_optimiser)):
-            o = 0
-            for p in params:
-                n = p.numel()
-                p.grad = grad[o:o + n].view_as(p)
-                st = opt.state[p]
-                st["step"] = self._step_t
-                if self.optim_name == "adam":   # torch.optim.Adam's state keys, in its order
-                    st["exp_avg"] = m[o:o + n].view_as(p)
-                    st["exp_avg_sq"] = sq[o:o + n].view_as(p)
-                else:
-                    st["square_avg"] = sq[o:o + n].view_as(p)
-                o += n
+            link(params, opt, grad, dict(step=self._step_t, **state_buffers(self.optim_name, sq, m)))
         self._handle = None
 
     def _get_handle(self, batch):
@@ -246,39 +233,23 @@ class ActorCriticLearner:
         _lib.check(self._handle.lib.ma_update_targets(self._handle.h, float(tau), _lib.stream_ptr()))
 
     def _update_targets(self):
-        if self._critic.is_cuda and self._handle is not None:
-            _lib.check(self._handle.lib.ma_update_targets(self._handle.h, 0.0, _lib.stream_ptr()))
-        else:
-            with th.no_grad():
-                self._tcritic.copy_(self._critic)
-        self.logger.console_logger.info("Updated target network")
+        hard_target_update(self._handle, "ma_update_targets", self._tcritic, self._critic, self.logger, 0.0)
 
     def cuda(self):
-        dev = th.device("cuda", th.cuda.current_device())
-        for name in ("_agent", "_critic", "_tcritic", "_agrad", "_asq", "_cgrad", "_csq", "_am", "_cm", "_stats",
-                     "rew_ms"):
-            t = getattr(self, name)
-            if t is not None:
-                setattr(self, name, t.to(dev))
+        to_current_device(self, ("_agent", "_critic", "_tcritic", "_agrad", "_asq", "_cgrad", "_csq", "_am", "_cm",
+                                 "_stats", "rew_ms"))
         self._relink()
 
     def reward_stats(self):
         """The running reward statistics as a dict of Python floats: mean, var, count (synchronises)."""
-        if self.rew_ms is None:
-            raise _lib.MQError("reward_stats() needs standardise_rewards: True")
-        m, v, c = self.rew_ms.tolist()
-        return dict(mean=m, var=v, count=c)
+        return reward_stats(self.rew_ms)
 
     def save_models(self, path):
         self.mac.save_models(path)
         th.save(self.critic.state_dict(), "{}/critic.th".format(path))
         for fname, opt in (("agent_opt.th", self.agent_optimiser), ("critic_opt.th", self.critic_optimiser)):
-            # per-parameter step tensors in the file, as torch writes them (the live state shares one counter)
-            sd = opt.state_dict()
-            sd["state"] = {i: dict(v, step=v["step"].clone()) if "step" in v else v for i, v in sd["state"].items()}
-            th.save(sd, "{}/{}".format(path, fname))
-        if self.rew_ms is not None:
-            th.save(self.reward_stats(), "{}/rew_ms.th".format(path))
+            th.save(state_dict_own_steps(opt), "{}/{}".format(path, fname))
+        save_rew_ms(self.rew_ms, path)
 
     def load_models(self, path):
         ml = lambda s, loc: s  # noqa: E731
@@ -286,40 +257,15 @@ class ActorCriticLearner:
         self.critic.load_state_dict(th.load("{}/critic.th".format(path), map_location=ml, weights_only=True))
         # the target critic is not saved (as the COMA learner): it restarts from the critic
         self.target_critic.load_state_dict(self.critic.state_dict())
-        keys = ("exp_avg", "exp_avg_sq") if self.optim_name == "adam" else ("square_avg",)
         steps = []
-        for fname, opt, params, bufs in (
-                ("agent_opt.th", self.agent_optimiser, self.agent_params, (self._am, self._asq)),
-                ("critic_opt.th", self.critic_optimiser, self.critic_params, (self._cm, self._csq))):
+        for fname, opt, params, sq, m in (("agent_opt.th", self.agent_optimiser, self.agent_params, self._asq, self._am),
+                                          ("critic_opt.th", self.critic_optimiser, self.critic_params, self._csq,
+                                           self._cm)):
             sd = th.load("{}/{}".format(path, fname), map_location=ml, weights_only=True)
-            groups = sd.get("param_groups") or [{}]
-            wrote = "adam" if "betas" in groups[0] else "rmsprop" if "alpha" in groups[0] else None
-            if wrote is not None and wrote != self.optim_name:
-                raise ValueError("{}/{} was written by {}, but this learner runs optimizer: {}.".format(
-                    path, fname, wrote, self.optim_name))
-            opt.load_state_dict(sd)
-            flat = dict(zip(keys, bufs if self.optim_name == "adam" else bufs[1:]))
-            o = 0
-            for p in params:
-                n = p.numel()
-                st = opt.state.get(p, {})
-                for key, buf in flat.items():
-                    if key in st:
-                        buf[o:o + n].copy_(st[key].reshape(-1))
-                if "step" in st:
-                    steps.append(float(st["step"]))
-                o += n
-        self._opt_steps = int(steps[0]) if steps else 0
-        if self.rew_ms is not None:
-            f = "{}/rew_ms.th".format(path)
-            if os.path.exists(f):
-                ms = th.load(f, map_location=ml, weights_only=True)
-                vals = [float(ms["mean"]), float(ms["var"]), float(ms["count"])]
-            else:
-                vals = list(REW_MS_INIT)
-                self.logger.console_logger.warning(
-                    "{} not found: standardise_rewards starts from fresh reward statistics".format(f))
-            self.rew_ms.copy_(th.tensor(vals, dtype=th.float64))
+            steps.append(load_state(opt, sd, params, state_buffers(self.optim_name, sq, m), expect=self.optim_name,
+                                    what="{}/{}".format(path, fname)))
+        self._opt_steps = next((n for n in steps if n is not None), 0)
+        load_rew_ms(self.rew_ms, path, self.logger)
         self._relink()
 
     # -- extras (parity / diagnostics) -----------------------------------------------------------------------
@@ -337,11 +283,7 @@ class ActorCriticLearner:
         before the 1 / M scale, (B, T, n, A)."""
         B, Tp = self._last_batch
         T, n, A = Tp - 1, self.n_agents, self.n_actions
-        cnt = ctypes.c_int64()
-        h = self._handle
-        _lib.check(h.lib.ma_copy_intermediate(h.h, which, None, ctypes.byref(cnt), None))
-        out = th.empty(cnt.value, dtype=th.float32, device=self._agent.device)
-        _lib.check(h.lib.ma_copy_intermediate(h.h, which, _lib.ptr(out), ctypes.byref(cnt), _lib.stream_ptr()))
+        out = self._handle.copy_intermediate(which, self._agent.device)
         if which == 0:
             return out.view(Tp, B, n).permute(1, 0, 2)
         if which in (1, 2):

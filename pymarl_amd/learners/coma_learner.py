@@ -37,12 +37,13 @@ import torch as th
 from torch.optim import RMSprop
 
 from .. import _lib
-from ..modules.agents.rnn_agent import use_rnn_config
+from ..components.episode_buffer import is_per_batch, is_replay_view, replay_view
+from ..modules.agents.rnn_agent import obs_dim, state_dim, use_rnn_config
 from ..modules.critics.coma import COMACritic
-from ..modules.flat import pack, rebind
-from .dp import DPCheck, SharedComm, dp_world, local_shard, native_comm_wanted, shard_bounds
-from .q_learner import is_per_batch, replay_view
-from ..components.episode_buffer import is_replay_view
+from ..modules.flat import link, load_state, pack, rebind, to_current_device
+from .dp import (DPCheck, SharedComm, allreduce_grad_buffer, dp_active, dp_collective, dp_world, local_shard,
+                 native_comm_wanted, shard_bounds)
+from .keys import hard_target_update
 
 CC_MAXR = 80   # coma_chain.hpp: most critic rows (B * n_agents) the persistent chain takes
 
@@ -51,10 +52,8 @@ def make_coma_config(args, input_dim, max_batch, max_seq):
     cfg = _lib.MCConfig()
     cfg.n_agents = args.n_agents
     cfg.n_actions = args.n_actions
-    cfg.obs_dim = int(input_dim - (args.n_actions if args.obs_last_action else 0) -
-                      (args.n_agents if args.obs_agent_id else 0))
-    st = getattr(args, "state_shape", 1)
-    cfg.state_dim = int(st if isinstance(st, int) else th.Size(st).numel())
+    cfg.obs_dim = obs_dim(args, input_dim)
+    cfg.state_dim = state_dim(args)
     cfg.rnn_hidden_dim = args.rnn_hidden_dim
     cfg.obs_last_action = int(bool(args.obs_last_action))
     cfg.obs_agent_id = int(bool(args.obs_agent_id))
@@ -128,16 +127,9 @@ class COMALearner:
         self.mac.agent._flat = self._agent
         self.critic._flat = self._critic
         self.target_critic._flat = self._tcritic
-        for params, grad, sq, opt in ((self.agent_params, self._agrad, self._asq, self.agent_optimiser),
-                                      (self.critic_params, self._cgrad, self._csq, self.critic_optimiser)):
-            o = 0
-            for p in params:
-                n = p.numel()
-                p.grad = grad[o:o + n].view_as(p)
-                st = opt.state[p]
-                st["square_avg"] = sq[o:o + n].view_as(p)
-                st.setdefault("step", th.tensor(0.0))
-                o += n
+        # a step tensor per parameter: train() advances the agent's by 1 and the critic's by its live steps
+        link(self.agent_params, self.agent_optimiser, self._agrad, {"square_avg": self._asq})
+        link(self.critic_params, self.critic_optimiser, self._cgrad, {"square_avg": self._csq})
         self._handle = None
 
     def _get_handle(self, batch):
@@ -167,11 +159,7 @@ class COMALearner:
             self._handle, self._handle_key = h, (need_b, T)
         return self._handle
 
-    def _dp_active(self):
-        if not self.dp:
-            return False
-        import torch.distributed as dist
-        return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    _dp_active, collective = dp_active, dp_collective
 
     def dp_mode(self, batch_size):
         """None (not data parallel), "replicated" or "exchange" for a global batch of `batch_size` episodes."""
@@ -184,16 +172,9 @@ class COMALearner:
             raise ValueError("coma_dp_mode {!r} not recognised".format(mode))
         return mode
 
-    def collective(self):
-        """"rccl-native", "torch.distributed" (callbacks) or None, for the last handle."""
-        if not self._dp_active():
-            return None
-        return "rccl-native" if (self._handle is not None and self._handle.native) else "torch.distributed"
-
     def _allreduce(self, ptr, count, stream, ctx):
         """mc_allreduce_fn: sum `count` floats of one of our own device buffers over the ranks, in stream order."""
         try:
-            from .dp import allreduce_grad_buffer
             for base in (self._cgrad, self._agrad, self._dp_scratch):
                 if base is not None and base.data_ptr() == ptr and count <= base.numel():
                     allreduce_grad_buffer(base[:count])
@@ -259,17 +240,10 @@ class COMALearner:
             self.log_stats_t = t_env
 
     def _update_targets(self):
-        if self._critic.is_cuda and self._handle is not None:
-            _lib.check(self._handle.lib.mc_update_targets(self._handle.h, _lib.stream_ptr()))
-        else:
-            with th.no_grad():
-                self._tcritic.copy_(self._critic)
-        self.logger.console_logger.info("Updated target network")
+        hard_target_update(self._handle, "mc_update_targets", self._tcritic, self._critic, self.logger)
 
     def cuda(self):
-        dev = th.device("cuda", th.cuda.current_device())
-        for name in ("_agent", "_critic", "_tcritic", "_agrad", "_asq", "_cgrad", "_csq", "_stats"):
-            setattr(self, name, getattr(self, name).to(dev))
+        to_current_device(self, ("_agent", "_critic", "_tcritic", "_agrad", "_asq", "_cgrad", "_csq", "_stats"))
         self._relink()
 
     def save_models(self, path):
@@ -286,14 +260,9 @@ class COMALearner:
         self.target_critic.load_state_dict(self.critic.state_dict())
         for fname, opt, params, sq in (("agent_opt.th", self.agent_optimiser, self.agent_params, self._asq),
                                        ("critic_opt.th", self.critic_optimiser, self.critic_params, self._csq)):
-            opt.load_state_dict(th.load("{}/{}".format(path, fname), map_location=ml, weights_only=True))
-            o = 0
-            for p in params:
-                n = p.numel()
-                st = opt.state.get(p, {})
-                if "square_avg" in st:
-                    sq[o:o + n].copy_(st["square_avg"].reshape(-1))
-                o += n
+            # whichever optimiser wrote the file: this learner has never refused one
+            load_state(opt, th.load("{}/{}".format(path, fname), map_location=ml, weights_only=True), params,
+                       {"square_avg": sq})
         self._relink()
 
     # -- extras (parity / diagnostics) -----------------------------------------------------------------------
@@ -304,12 +273,8 @@ class COMALearner:
         """0: the critic Q values the actor used, (B, T, n, A); 1: TD(lambda) targets (B, T, n); 2: pi (B, T, n, A)."""
         B, Tp = self._last_batch
         T, n, A = Tp - 1, self.n_agents, self.n_actions
-        cnt = ctypes.c_int64()
-        h = self._handle
-        _lib.check(h.lib.mc_copy_intermediate(h.h, which, None, ctypes.byref(cnt), None))
-        out = th.empty(cnt.value, dtype=th.float32, device=self._agent.device)
-        _lib.check(h.lib.mc_copy_intermediate(h.h, which, _lib.ptr(out), ctypes.byref(cnt), _lib.stream_ptr()))
-        B = cnt.value // (T * n * (1 if which == 1 else A))   # pi has the actor's episodes (its shard when replicated)
+        out = self._handle.copy_intermediate(which, self._agent.device)
+        B = out.numel() // (T * n * (1 if which == 1 else A))   # pi has the actor's episodes (its shard when replicated)
         if which == 1:
             return out.view(T, B, n).permute(1, 0, 2)
         return out.view(T, B, n, A).permute(1, 0, 2, 3)

@@ -27,6 +27,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .. import _lib
+
 _COMM = {}
 
 
@@ -35,6 +37,19 @@ def dp_world():
     if dist.is_available() and dist.is_initialized():
         return dist.get_rank(), dist.get_world_size()
     return 0, 1
+
+
+def dp_active(learner):
+    """A learner's `_dp_active`: it asked for data parallelism (`learner.dp`) and there are ranks to share with."""
+    return learner.dp and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+
+
+def dp_collective(learner):
+    """A learner's `collective`: how a data-parallel step sums its gradient buffers, for the last handle:
+    "rccl-native" (the library's communicator), "torch.distributed", or None (not data parallel)."""
+    if not learner._dp_active():
+        return None
+    return "rccl-native" if (learner._handle is not None and learner._handle.native) else "torch.distributed"
 
 
 def native_comm_wanted(device):
@@ -49,7 +64,6 @@ def native_comm_wanted(device):
 
 def broadcast_comm_id(lib, device):
     """Rank 0's RCCL unique id (mq_comm_unique_id), shipped to every rank over the process group."""
-    from .. import _lib
     raw = (ctypes.c_uint8 * _lib.COMM_ID_BYTES)()
     if dist.get_rank() == 0:
         _lib.check(lib.mq_comm_unique_id(raw))
@@ -120,7 +134,6 @@ def batch_fingerprint(batch):
 
 def check_same_batch(batch, device, group=None):
     """Raise unless every rank passes the same global sample (one MAX all-reduce of [fp, -fp]; synchronises)."""
-    from .. import _lib
     fp = batch_fingerprint(batch)
     dev = device if (torch.device(device).type == "cuda" and dist.get_backend(group) == "nccl") else "cpu"
     t = torch.tensor([fp, -fp], dtype=torch.int64, device=dev)
@@ -193,7 +206,6 @@ class SharedComm:
 
     @classmethod
     def get(cls, lib, device):
-        from .. import _lib
         key = (torch.device(device).index, dist.get_world_size(), id(dist.group.WORLD))
         if cls._comm is None or cls._key != key:
             if cls._comm is not None:
@@ -208,7 +220,6 @@ class SharedComm:
     def lend(cls, handle, use, detach, device):
         """Attach the process communicator to `handle` (a _lib.Handle / ComaHandle) with `use` (mq_comm_use /
         mc_comm_use) and remember to detach it (`detach`) before the communicator is freed."""
-        from .. import _lib
         comm = cls.get(handle.lib, device)
         _lib.check(getattr(handle.lib, use)(handle.h, comm))
         cls._borrowers = [(r, d) for r, d in cls._borrowers if r() is not None]
@@ -230,7 +241,6 @@ class SharedComm:
         that still borrows it is detached first and falls back to `native = False`; the learner rebuilds it on its
         next train() (stale()), which re-attaches a new communicator."""
         if cls._comm is not None:
-            from .. import _lib
             for ref, detach in cls._borrowers:
                 h = ref()
                 if h is not None and getattr(h, "h", None) and h.h.value:

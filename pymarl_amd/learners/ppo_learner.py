@@ -22,7 +22,8 @@ import torch as th
 
 from .. import _lib
 from .actor_critic_learner import A2C_STATS, ActorCriticLearner, a2c_config
-from .q_learner import is_per_batch, replay_view
+from ..components.episode_buffer import is_per_batch, replay_view
+from ..modules.flat import to_current_device
 
 CRITIC_STATS = ("critic_loss", "critic_grad_norm", "td_error_abs", "q_taken_mean", "target_mean")
 PPO_STATS = A2C_STATS + ["clip_frac"]
@@ -91,7 +92,7 @@ class PPOLearner(ActorCriticLearner):
             self.log_stats_t = t_env
 
     def cuda(self):
-        self._estats = self._estats.to(th.device("cuda", th.cuda.current_device()))
+        to_current_device(self, ("_estats",))
         super().cuda()
 
     def last_stats(self):
@@ -106,9 +107,5 @@ class PPOLearner(ActorCriticLearner):
         if which not in (5, 6):
             return super().last_intermediate(which)
         B, Tp = self._last_batch
-        h = self._handle
-        cnt = ctypes.c_int64()
-        _lib.check(h.lib.ma_copy_intermediate(h.h, which, None, ctypes.byref(cnt), None))
-        out = th.empty(cnt.value, dtype=th.float32, device=self._agent.device)
-        _lib.check(h.lib.ma_copy_intermediate(h.h, which, _lib.ptr(out), ctypes.byref(cnt), _lib.stream_ptr()))
+        out = self._handle.copy_intermediate(which, self._agent.device)
         return out.view(Tp - 1, B, self.n_agents).permute(1, 0, 2)

@@ -34,211 +34,24 @@ from __future__ import annotations
 
 import copy
 import ctypes
-import numbers
 import os
-
-import numpy as np
 
 import torch as th
 from torch.optim import Adam, RMSprop
 
 from .. import _lib
-from ..components.episode_buffer import PrioritizedBatch, is_replay_view
-from ..modules.agents.rnn_agent import agent_kind, hidden_dim
-from ..modules.flat import pack, rebind
-from .dp import DPCheck, SharedComm, allreduce_grad_buffer, dp_world, local_shard, native_comm_wanted
-from ..modules.mixers.qmix import QMixer, hypernet_config
+from ..components.episode_buffer import (_FIELDS, PrioritizedBatch, _field_view, is_per_batch,  # noqa: F401
+                                         is_replay_view, replay_view)
+from ..modules.agents.rnn_agent import Q_TARGETS, make_config  # noqa: F401
+from ..modules.flat import link, load_state, pack, rebind, state_buffers, state_dict_own_steps, to_current_device
+from .dp import (DPCheck, SharedComm, allreduce_grad_buffer, dp_active, dp_collective, dp_world, local_shard,
+                 native_comm_wanted)
+from .keys import (OPTIMIZERS, REW_MS_INIT, hard_target_update, load_rew_ms, optimizer_config,  # noqa: F401
+                   reward_norm_config, reward_stats, save_rew_ms, target_update_config)
+from ..modules.mixers.qmix import QMixer
 from ..modules.mixers.vdn import VDNMixer
 
 MIXER_IDS = {None: _lib.MIXER_NONE, "vdn": _lib.MIXER_VDN, "qmix": _lib.MIXER_QMIX}
-Q_TARGETS = ("one_step", "td_lambda")
-OPTIMIZERS = ("rmsprop", "adam")
-_FIELDS = [("obs", th.float32), ("state", th.float32), ("actions", th.int64), ("avail_actions", th.int32),
-           ("reward", th.float32), ("terminated", th.uint8), ("filled", th.int64)]
-
-
-def make_config(args, mixer, input_dim=None, max_batch=1, max_seq=2):
-    cfg = _lib.MQConfig()
-    cfg.n_agents = args.n_agents
-    cfg.n_actions = args.n_actions
-    obs = getattr(args, "obs_shape", None)
-    if obs is None and input_dim is not None:
-        obs = input_dim - (args.n_actions if args.obs_last_action else 0) - (args.n_agents if args.obs_agent_id else 0)
-    cfg.obs_dim = int(obs)
-    st = getattr(args, "state_shape", 1)
-    cfg.state_dim = int(st if isinstance(st, int) else th.Size(st).numel())
-    cfg.rnn_hidden_dim = hidden_dim(args)   # epymarl's hidden_dim when rnn_hidden_dim is absent
-    # epymarl's use_rnn: False selects the feed-forward agent (rnn = Linear + ReLU); absent or True: the GRU
-    cfg.agent = agent_kind(args)
-    cfg.mixing_embed_dim = getattr(args, "mixing_embed_dim", 32)
-    cfg.mixer = mixer
-    cfg.double_q = int(bool(getattr(args, "double_q", True)))
-    cfg.obs_last_action = int(bool(args.obs_last_action))
-    cfg.obs_agent_id = int(bool(args.obs_agent_id))
-    cfg.gamma = getattr(args, "gamma", 0.99)
-    cfg.lr = getattr(args, "lr", 5e-4)
-    cfg.optim_alpha = getattr(args, "optim_alpha", 0.99)
-    cfg.optim_eps = getattr(args, "optim_eps", 1e-5)
-    cfg.grad_norm_clip = getattr(args, "grad_norm_clip", 10.0)
-    cfg.max_batch = int(max_batch)
-    cfg.max_seq = int(max_seq)
-    # opt-in masked Huber TD loss (north_star; the reference has L2 only, q_learner.py:96-97): td_loss: huber,
-    # huber_delta (default 1.0); anything else keeps L2
-    cfg.huber_delta = float(getattr(args, "huber_delta", 1.0)) if getattr(args, "td_loss", "l2") == "huber" else 0.0
-    # opt-in TD(lambda) targets (the reference's Q learner has the one-step target only, q_learner.py:86; the
-    # function is its rl_utils.build_td_lambda_targets): q_targets: td_lambda selects them with args.td_lambda.
-    # Without it args.td_lambda is ignored: COMA-style configs carry td_lambda: 0.8 globally
-    q_targets = getattr(args, "q_targets", "one_step")
-    if q_targets not in Q_TARGETS:
-        raise ValueError("q_targets {} not recognised (one of {}).".format(q_targets, ", ".join(Q_TARGETS)))
-    cfg.td_lambda = float(args.td_lambda) if q_targets == "td_lambda" else 0.0
-    # upstream PyMARL's two-layer QMIX hypernetwork (hypernet_layers: 2, hypernet_embed); VDN / IQL ignore the keys
-    if mixer == _lib.MIXER_QMIX:
-        cfg.hypernet_layers, cfg.hypernet_embed = hypernet_config(args)
-    return cfg
-
-
-def optimizer_config(args):
-    """The optimiser keys, named as pymarl2 names them: (name, kwargs). optimizer absent or "rmsprop": ("rmsprop",
-    None), the reference's RMSprop(lr, optim_alpha, optim_eps). "adam": torch.optim.Adam's lr, betas (adam_betas,
-    default (0.9, 0.999)), eps (adam_eps, default 1e-8: torch's, pymarl2 does not pass optim_eps to Adam) and
-    weight_decay (default 0, L2). Anything else, or adam_amsgrad: True, raises ValueError."""
-    name = getattr(args, "optimizer", None)
-    name = "rmsprop" if name is None else name
-    if name not in OPTIMIZERS:
-        raise ValueError("optimizer {} not recognised (one of {}).".format(name, ", ".join(OPTIMIZERS)))
-    if name == "rmsprop":
-        return name, None
-    if getattr(args, "adam_amsgrad", False):
-        raise ValueError("adam_amsgrad is not supported (optimizer: adam runs torch.optim.Adam's non-amsgrad step).")
-    betas = tuple(float(b) for b in getattr(args, "adam_betas", (0.9, 0.999)))
-    eps, wd = float(getattr(args, "adam_eps", 1e-8)), float(getattr(args, "weight_decay", 0.0))
-    if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
-        raise ValueError("adam_betas must be two values in [0, 1), got {}.".format(betas))
-    if not eps > 0.0:
-        raise ValueError("adam_eps must be > 0, got {}.".format(eps))
-    if not wd >= 0.0:
-        raise ValueError("weight_decay must be >= 0, got {}.".format(wd))
-    return name, dict(lr=args.lr, betas=betas, eps=eps, weight_decay=wd)
-
-
-def target_update_config(args):
-    """epymarl's target_update_interval_or_tau: (mode, value). Key absent or None: (None, None), the reference's
-    episode-counted target_update_interval applies. v > 1: ("hard", v), a hard update every v TRAINING STEPS
-    (target_update_interval is then ignored). 0 < v <= 1: ("soft", v), a Polyak update with tau = v after every step.
-    v <= 0, NaN or not a number (a bool is not one): ValueError."""
-    v = getattr(args, "target_update_interval_or_tau", None)
-    if v is None:
-        return None, None
-    if isinstance(v, bool) or not isinstance(v, numbers.Real):
-        raise ValueError("target_update_interval_or_tau must be a number, got {!r}.".format(v))
-    v = float(v)
-    if not v > 0.0:   # NaN too
-        raise ValueError("target_update_interval_or_tau must be > 0 (above 1: a hard update every that many training "
-                         "steps; at most 1: the soft update's tau), got {}.".format(v))
-    return ("hard", v) if v > 1.0 else ("soft", v)
-
-
-def reward_norm_config(args):
-    """epymarl's standardise_rewards: True standardises the rewards with running statistics before the TD target is
-    formed. Key absent: False (epymarl's own default is True: its configs carry the key). Not a bool: ValueError; with
-    learner_dp: ValueError (each rank would see only its shard's rewards)."""
-    v = getattr(args, "standardise_rewards", False)
-    if v is None:
-        return False
-    if not isinstance(v, (bool, np.bool_)):
-        raise ValueError("standardise_rewards must be True or False, got {!r}.".format(v))
-    if v and getattr(args, "learner_dp", False):
-        raise ValueError("learner_dp is not supported with standardise_rewards: the running reward statistics belong "
-                         "to one device's batches, and each rank would see only its shard")
-    return bool(v)
-
-
-REW_MS_INIT = (0.0, 1.0, 1e-4)   # running (mean, var, count) of a fresh learner, epymarl's RunningMeanStd
-
-
-def is_per_batch(batch):
-    """True for a PrioritizedReplayBuffer sample: train() runs it as a prioritized-replay step."""
-    return isinstance(batch, PrioritizedBatch)
-
-
-def _field_view(t, dtype):
-    """(tensor usable by the kernels, t_stride): [B][T][...] with trailing dims contiguous and the right dtype."""
-    if t.dtype != dtype:
-        t = t.to(dtype)
-    inner = 1
-    for s in t.shape[2:]:
-        inner *= s
-    ok = t.stride(1) == inner and t.stride(0) % max(1, inner) == 0 and t[0, 0].is_contiguous()
-    if not ok:
-        t = t.contiguous()
-    return t, t.stride(0) // max(1, inner)
-
-
-def replay_view(batch, avail_bits=True):
-    """MQReplay for an EpisodeBatch (episode-major storage) or a SampledBatch (storage + device ids).
-    Returns (struct, keepalive) — keep the second alive until the kernels that read it have been queued.
-    avail_bits: hand the kernels the buffer's avail bitmask (ReplayBuffer.avail_bits_current: rebuilt first if the
-    storage was written behind its back), else they read the int32 avail_actions rows."""
-    keep = []
-    rep = _lib.MQReplay()
-    if is_replay_view(batch):
-        src = batch.source.data.transition_data
-        tstride = batch.source.max_seq_length
-        if is_per_batch(batch):
-            # prioritized replay: the ids were written by the sampler kernel and exist on the device only
-            ids = batch.ep_ids
-            keep.append(ids)
-            rep.ep_ids = ids.data_ptr()
-            rep.ep_ids_host = None
-        elif len(batch.ep_ids_np) <= _lib.INLINE_IDS:
-            # ids travel in the kernel arguments: no host-to-device copy on the step's stream
-            host = np.ascontiguousarray(batch.ep_ids_np, dtype=np.int64)
-            keep.append(host)
-            rep.ep_ids_host = host.ctypes.data
-            rep.ep_ids = None
-        else:
-            ids = batch.ep_ids
-            keep.append(ids)
-            rep.ep_ids = ids.data_ptr()
-        rep.n_episodes = batch.source.batch_size
-        rep.t_len = batch.t_len
-        tensors = {}
-        for k, dt in _FIELDS:
-            if k not in src:
-                continue
-            t = src[k]
-            if t.dtype != dt or not t.is_contiguous():
-                raise _lib.MQError("replay field {} must be a contiguous {} tensor".format(k, dt))
-            tensors[k] = t
-        cur = getattr(batch.source, "avail_bits_current", None)
-        bits = cur() if (avail_bits and cur is not None) else None
-        if bits is not None:
-            keep.append(bits)
-            rep.avail_bits = bits.data_ptr()
-    else:
-        src = batch.data.transition_data
-        tensors, strides = {}, set()
-        for k, dt in _FIELDS:
-            if k not in src:
-                continue
-            t, ts = _field_view(src[k], dt)
-            tensors[k] = t
-            strides.add(ts)
-        if len(strides) != 1:
-            tensors = {k: v.contiguous() for k, v in tensors.items()}
-            strides = {batch.max_seq_length}
-        tstride = strides.pop()
-        rep.ep_ids = None
-        rep.n_episodes = batch.batch_size
-        rep.t_len = batch.max_seq_length
-    for k, t in tensors.items():
-        keep.append(t)
-        setattr(rep, k, t.data_ptr())
-    _lib.require_gpu(tensors["obs"])
-    rep.batch_size = batch.batch_size
-    rep.t_stride = int(tstride)
-    return rep, keep
 
 
 class QLearner:
@@ -314,27 +127,15 @@ class QLearner:
         if self.mixer is not None and hasattr(self.mixer, "_flat"):
             self.mixer._flat = self._online[Pa:self.n_params]
             self.target_mixer._flat = self._target[Pa:self.n_params]
+        # one shared step counter: train() increments it once, not once per parameter
         self._step_t = th.tensor(float(getattr(self, "_opt_steps", 0)))
-        o = 0
-        for p in self.params:
-            n = p.numel()
-            p.grad = self._grad[o:o + n].view_as(p)
-            st = self.optimiser.state[p]
-            if self.optim_name == "adam":   # torch.optim.Adam's state keys, in its order
-                st["step"] = self._step_t
-                st["exp_avg"] = self._m[o:o + n].view_as(p)
-                st["exp_avg_sq"] = self._sq[o:o + n].view_as(p)
-            else:
-                st["square_avg"] = self._sq[o:o + n].view_as(p)
-                st["step"] = self._step_t   # one shared counter: train() increments it once, not once per parameter
-            o += n
+        bufs = state_buffers(self.optim_name, self._sq, self._m)
+        # where each optimiser's state has had its step here: Adam's first (torch's order), RMSprop's last
+        link(self.params, self.optimiser, self._grad,
+             dict(step=self._step_t, **bufs) if self.optim_name == "adam" else dict(bufs, step=self._step_t))
         self._handle = None
 
-    def _dp_active(self):
-        if not self.dp:
-            return False
-        import torch.distributed as dist
-        return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    _dp_active, collective = dp_active, dp_collective
 
     def _local_batch(self, batch):
         """Data parallel: this rank's shard of the global sample (dp.local_shard), the ranks' agreement checked per
@@ -450,46 +251,24 @@ class QLearner:
         # "soft": the step's last launch already moved the targets (mq_set_soft_target); nothing to do or to print
 
     def _update_targets(self):
-        if self._online.is_cuda and self._handle is not None:
-            _lib.check(self._handle.lib.mq_update_targets(self._handle.h, _lib.stream_ptr()))
-        else:
-            with th.no_grad():
-                self._target.copy_(self._online)
-        self.logger.console_logger.info("Updated target network")
+        hard_target_update(self._handle, "mq_update_targets", self._target, self._online, self.logger)
 
     def cuda(self):
-        dev = th.device("cuda", th.cuda.current_device())
-        self._online = self._online.to(dev)
-        self._target = self._target.to(dev)
-        self._grad = self._grad.to(dev)
-        self._sq = self._sq.to(dev)
-        if self._m is not None:
-            self._m = self._m.to(dev)
-        self._stats = self._stats.to(dev)
-        if self.rew_ms is not None:
-            self.rew_ms = self.rew_ms.to(dev)
+        to_current_device(self, ("_online", "_target", "_grad", "_sq", "_m", "_stats", "rew_ms"))
         self._relink()
 
     def reward_stats(self):
         """The running reward statistics as a dict of Python floats: mean, var, count (synchronises)."""
-        if self.rew_ms is None:
-            raise _lib.MQError("reward_stats() needs standardise_rewards: True")
-        m, v, c = self.rew_ms.tolist()
-        return dict(mean=m, var=v, count=c)
+        return reward_stats(self.rew_ms)
 
     def save_models(self, path):
         self.mac.save_models(path)
         if self.mixer is not None:
             th.save(self.mixer.state_dict(), "{}/mixer.th".format(path))
-        # per-parameter step tensors in the file, as torch's RMSprop writes them: the live state shares one counter,
-        # and a loader that kept it shared would count every parameter's update into it
-        sd = self.optimiser.state_dict()
-        sd["state"] = {i: dict(v, step=v["step"].clone()) if "step" in v else v for i, v in sd["state"].items()}
-        th.save(sd, "{}/opt.th".format(path))
+        th.save(state_dict_own_steps(self.optimiser), "{}/opt.th".format(path))
         # the epymarl keys' state, as plain dicts of Python numbers: the running reward statistics, and the counters
         # of the step-counted target schedule
-        if self.rew_ms is not None:
-            th.save(self.reward_stats(), "{}/rew_ms.th".format(path))
+        save_rew_ms(self.rew_ms, path)
         if self.target_mode is not None:
             th.save(dict(training_steps=int(self.training_steps),
                          last_target_update_step=int(self.last_target_update_step)),
@@ -503,36 +282,11 @@ class QLearner:
         if self.mixer is not None:
             self.mixer.load_state_dict(th.load("{}/mixer.th".format(path), map_location=ml, weights_only=True))
         sd = th.load("{}/opt.th".format(path), map_location=ml, weights_only=True)
-        # an opt.th of the other optimiser would load without complaint (torch checks only the group sizes) and
-        # leave the moments this learner steps with at zero
-        groups = sd.get("param_groups") or [{}]
-        wrote = "adam" if "betas" in groups[0] else "rmsprop" if "alpha" in groups[0] else None
-        if wrote is not None and wrote != self.optim_name:
-            raise ValueError("{}/opt.th was written by {}, but this learner runs optimizer: {}.".format(
-                path, {"adam": "Adam", "rmsprop": "RMSprop"}[wrote], self.optim_name))
-        self.optimiser.load_state_dict(sd)
-        # load_state_dict replaced the state tensors: copy back into the flat buffers
-        flat = {"exp_avg": self._m, "exp_avg_sq": self._sq} if self.optim_name == "adam" else {"square_avg": self._sq}
-        o = 0
-        for p in self.params:
-            n = p.numel()
-            st = self.optimiser.state.get(p, {})
-            for key, buf in flat.items():
-                if key in st:
-                    buf[o:o + n].copy_(st[key].reshape(-1))
-            o += n
-        steps = [float(self.optimiser.state[p]["step"]) for p in self.params if "step" in self.optimiser.state[p]]
-        self._opt_steps = int(steps[0]) if steps else 0
-        if self.rew_ms is not None:
-            f = "{}/rew_ms.th".format(path)
-            if os.path.exists(f):
-                ms = th.load(f, map_location=ml, weights_only=True)
-                vals = [float(ms["mean"]), float(ms["var"]), float(ms["count"])]
-            else:   # a checkpoint written without standardise_rewards: start the statistics afresh, and say so
-                vals = list(REW_MS_INIT)
-                self.logger.console_logger.warning(
-                    "{} not found: standardise_rewards starts from fresh reward statistics".format(f))
-            self.rew_ms.copy_(th.tensor(vals, dtype=th.float64))
+        # load_state_dict replaces the state tensors: copied back into the flat buffers, and re-linked below
+        self._opt_steps = load_state(self.optimiser, sd, self.params, state_buffers(self.optim_name, self._sq, self._m),
+                                     expect=self.optim_name, what="{}/opt.th".format(path),
+                                     names={"adam": "Adam", "rmsprop": "RMSprop"}.get) or 0
+        load_rew_ms(self.rew_ms, path, self.logger)
         if self.target_mode is not None:
             f = "{}/target_update.th".format(path)
             if os.path.exists(f):
@@ -542,13 +296,6 @@ class QLearner:
         self._relink()
 
     # -- extras (parity / diagnostics) -----------------------------------------------------------------------
-    def collective(self):
-        """How a data-parallel step sums the gradient buffer: "rccl-native" (the library's communicator),
-        "torch.distributed", or None (not data parallel)."""
-        if not self._dp_active():
-            return None
-        return "rccl-native" if (self._handle is not None and self._handle.native) else "torch.distributed"
-
     def last_stats(self):
         """dict of the last step's stats (loss, grad_norm, td_error_abs, q_taken_mean, target_mean, mask_sum)."""
         st = self._stats.tolist()
@@ -599,11 +346,7 @@ class QLearner:
         (B, T+1, n, 64)."""
         B, Tp = self._last_batch
         n, A = self.args.n_agents, self.args.n_actions
-        cnt = ctypes.c_int64()
-        h = self._handle
-        _lib.check(h.lib.mq_copy_intermediate(h.h, which, None, ctypes.byref(cnt), None))
-        out = th.empty(cnt.value, dtype=th.float32, device=self._online.device)
-        _lib.check(h.lib.mq_copy_intermediate(h.h, which, _lib.ptr(out), ctypes.byref(cnt), _lib.stream_ptr()))
+        out = self._handle.copy_intermediate(which, self._online.device)
         if which in (0, 1):
             return out.view(Tp, B, n, A).permute(1, 0, 2, 3)
         if which in (3, 9):

@@ -16,6 +16,9 @@ import torch.nn as nn
 
 from ... import _lib
 from ..flat import FlatModule
+from ..mixers.qmix import hypernet_config
+
+Q_TARGETS = ("one_step", "td_lambda")
 
 
 def input_dim(input_shape):
@@ -53,6 +56,58 @@ def agent_kind(args):
     return _lib.AGENT_GRU if use_rnn_config(args) else _lib.AGENT_FFN
 
 
+def obs_dim(args, width):
+    """The observation's share of an agent input of `width` values (the last action and the agent id follow it)."""
+    return int(width - (args.n_actions if args.obs_last_action else 0) - (args.n_agents if args.obs_agent_id else 0))
+
+
+def state_dim(args):
+    st = getattr(args, "state_shape", 1)
+    return int(st if isinstance(st, int) else th.Size(st).numel())
+
+
+def make_config(args, mixer, input_dim=None, max_batch=1, max_seq=2):
+    """mq_config of `args` for the Q learner's step (learners/q_learner.py) or, with mixer MIXER_NONE, the agent's own
+    inference handle."""
+    cfg = _lib.MQConfig()
+    cfg.n_agents = args.n_agents
+    cfg.n_actions = args.n_actions
+    obs = getattr(args, "obs_shape", None)
+    if obs is None and input_dim is not None:
+        obs = obs_dim(args, input_dim)
+    cfg.obs_dim = int(obs)
+    cfg.state_dim = state_dim(args)
+    cfg.rnn_hidden_dim = hidden_dim(args)   # epymarl's hidden_dim when rnn_hidden_dim is absent
+    # epymarl's use_rnn: False selects the feed-forward agent (rnn = Linear + ReLU); absent or True: the GRU
+    cfg.agent = agent_kind(args)
+    cfg.mixing_embed_dim = getattr(args, "mixing_embed_dim", 32)
+    cfg.mixer = mixer
+    cfg.double_q = int(bool(getattr(args, "double_q", True)))
+    cfg.obs_last_action = int(bool(args.obs_last_action))
+    cfg.obs_agent_id = int(bool(args.obs_agent_id))
+    cfg.gamma = getattr(args, "gamma", 0.99)
+    cfg.lr = getattr(args, "lr", 5e-4)
+    cfg.optim_alpha = getattr(args, "optim_alpha", 0.99)
+    cfg.optim_eps = getattr(args, "optim_eps", 1e-5)
+    cfg.grad_norm_clip = getattr(args, "grad_norm_clip", 10.0)
+    cfg.max_batch = int(max_batch)
+    cfg.max_seq = int(max_seq)
+    # opt-in masked Huber TD loss (north_star; the reference has L2 only, q_learner.py:96-97): td_loss: huber,
+    # huber_delta (default 1.0); anything else keeps L2
+    cfg.huber_delta = float(getattr(args, "huber_delta", 1.0)) if getattr(args, "td_loss", "l2") == "huber" else 0.0
+    # opt-in TD(lambda) targets (the reference's Q learner has the one-step target only, q_learner.py:86; the
+    # function is its rl_utils.build_td_lambda_targets): q_targets: td_lambda selects them with args.td_lambda.
+    # Without it args.td_lambda is ignored: COMA-style configs carry td_lambda: 0.8 globally
+    q_targets = getattr(args, "q_targets", "one_step")
+    if q_targets not in Q_TARGETS:
+        raise ValueError("q_targets {} not recognised (one of {}).".format(q_targets, ", ".join(Q_TARGETS)))
+    cfg.td_lambda = float(args.td_lambda) if q_targets == "td_lambda" else 0.0
+    # upstream PyMARL's two-layer QMIX hypernetwork (hypernet_layers: 2, hypernet_embed); VDN / IQL ignore the keys
+    if mixer == _lib.MIXER_QMIX:
+        cfg.hypernet_layers, cfg.hypernet_embed = hypernet_config(args)
+    return cfg
+
+
 class RNNAgent(FlatModule):
     def __init__(self, input_shape, args):
         super().__init__()
@@ -75,7 +130,6 @@ class RNNAgent(FlatModule):
 
     def handle(self):
         """Inference handle (agent-only layout) bound to this module's flat parameters."""
-        from ...learners.q_learner import make_config
         if self._handle is None or self._handle[1] != self._flat.data_ptr():
             cfg = make_config(self.args, mixer=_lib.MIXER_NONE, input_dim=self.input_dim, max_batch=1, max_seq=2)
             h = _lib.Handle(cfg)

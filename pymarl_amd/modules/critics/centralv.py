@@ -15,6 +15,7 @@ import torch as th
 import torch.nn as nn
 
 from ... import _lib
+from ...components.episode_buffer import replay_view
 from ..flat import FlatModule
 
 CRITIC_WIDTHS = (64, 128)
@@ -73,7 +74,6 @@ class VCritic(FlatModule):
 
     def forward(self, batch, t=None):
         """v (bs, max_t, n_agents, 1) for every stored step (t=None) or step t (max_t = 1)."""
-        from ...learners.q_learner import replay_view
         rep, keep = replay_view(batch)
         _lib.require_gpu(self._flat)
         tq = rep.t_len if t is None else 1

@@ -11,6 +11,7 @@ import torch as th
 import torch.nn as nn
 
 from ... import _lib
+from ...components.episode_buffer import replay_view
 from ..flat import FlatModule
 
 CRITIC_HIDDEN = 128   # coma.py:17-19
@@ -51,7 +52,6 @@ class COMACritic(FlatModule):
 
     def forward(self, batch, t=None):
         """coma.py:22-27: q (bs, max_t, n_agents, n_actions) for every stored step (t=None) or step t (max_t=1)."""
-        from ...learners.q_learner import replay_view
         rep, keep = replay_view(batch)
         _lib.require_gpu(self._flat)
         tq = rep.t_len if t is None else 1

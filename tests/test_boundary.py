@@ -14,9 +14,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADERS = [os.path.join(ROOT, "include", h) for h in ("mq_learner.h", "mc_coma.h")]
 
 
-def declared_functions():
-    text = "".join(open(h).read() for h in HEADERS)
-    return sorted(set(re.findall(r"^\s*(?:const\s+)?\w+\*?\s+\*?(m[qc]_\w+)\s*\(", text, flags=re.M)))
+A2C_HEADER = os.path.join(ROOT, "include", "ma_a2c.h")
+# every ctypes.Structure _lib defines, under the C name of its class (MQConfig: mq_config, MAPpo: ma_ppo)
+STRUCTS = {c.__name__[:2].lower() + "_" + c.__name__[2:].lower(): c for c in vars(_lib).values()
+           if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure}
+CONSTANTS = {"MA_P_COUNT": "MA_P_COUNT", "MA_NTAIL": "MA_NTAIL", "MA_NSTATS": "MA_NSTATS", "MQ_INLINE_IDS": "INLINE_IDS",
+             "MQ_PER_MAX_LIVE": "PER_MAX_LIVE", "MQ_HYPERNET_EMBED_MAX": "HYPERNET_EMBED_MAX",
+             "MQ_COMM_ID_BYTES": "COMM_ID_BYTES"}
+
+
+def declared_functions(headers=HEADERS):
+    text = "".join(open(h).read() for h in headers)
+    return sorted(set(re.findall(r"^\s*(?:const\s+)?\w+\*?\s+\*?(m[qca]_\w+)\s*\(", text, flags=re.M)))
 
 
 def test_library_exports_every_declared_symbol():
@@ -56,6 +65,50 @@ int main(void) {
           _lib.MC_NTAIL, _lib.MC_NSTATS, ctypes.sizeof(_lib.MQPlan), _lib.MQPlan.inline_ids.offset,
           _lib.MQPlan.mix.offset, _lib.MQPlan.dwh.offset]
     assert c == py
+
+
+def test_a2c_header_declares_its_exports():
+    lib = _lib.load()
+    decl = declared_functions([A2C_HEADER])
+    assert decl == sorted(_lib.MA_EXPORTS)
+    assert declared_functions(HEADERS + [A2C_HEADER]) == sorted(_lib.EXPORTS + _lib.MA_EXPORTS)
+    for name in decl:
+        assert hasattr(lib, name), name
+
+
+@pytest.fixture(scope="module")
+def c_layout(tmp_path_factory):
+    """{name: value} from a probe the host compiler builds against the three headers: sizeof and every field offset
+    of every struct in STRUCTS (the fields come from the _fields_ lists), and the constants in CONSTANTS."""
+    lines = ['printf("{} %lld\\n", (long long){});'.format(c, c) for c in CONSTANTS]
+    for cname, cls in STRUCTS.items():
+        lines.append('printf("sizeof({0}) %zu\\n", sizeof({0}));'.format(cname))
+        lines += ['printf("{0}.{1} %zu\\n", offsetof({0}, {1}));'.format(cname, f) for f, _ in cls._fields_]
+    tmp = tmp_path_factory.mktemp("layout")
+    src, exe = tmp / "probe.c", tmp / "probe"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mc_coma.h"\n#include "ma_a2c.h"\n'
+                   "int main(void) {\n" + "\n".join(lines) + "\nreturn 0;\n}\n")
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    return {k: int(v) for k, v in (line.rsplit(" ", 1) for line in out.splitlines())}
+
+
+def test_every_struct_is_probed():
+    assert set(STRUCTS) >= {"mq_config", "mq_replay", "mq_plan", "mq_per", "mq_adam", "mc_config", "ma_config",
+                            "ma_adam", "ma_ppo", "ma_plan"}
+
+
+@pytest.mark.parametrize("cname", sorted(STRUCTS))
+def test_struct_size_and_every_field_offset(c_layout, cname):
+    cls = STRUCTS[cname]
+    assert ctypes.sizeof(cls) == c_layout["sizeof({})".format(cname)]
+    for f, _ in cls._fields_:
+        assert getattr(cls, f).offset == c_layout["{}.{}".format(cname, f)], f
+
+
+@pytest.mark.parametrize("cname", sorted(CONSTANTS))
+def test_mirrored_constant(c_layout, cname):
+    assert getattr(_lib, CONSTANTS[cname]) == c_layout[cname]
 
 
 def test_unknown_mixer_is_value_error_before_any_hip_call():
