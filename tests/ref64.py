@@ -4,8 +4,11 @@
 `[obs | last-action one-hot | agent id]`, fc1 -> relu -> GRU cell (or, under use_rnn: False, Linear -> relu) -> fc2,
 double-Q or max target, QMixer with a one- or two-layer hypernet / sum / none, the -9999999 masks and the masked L2
 loss. It shares no hand-derived backward with the numpy oracle (oracle/qlearner_np.py) or with the kernels; only
-constants are taken from the oracle. Huber and TD(lambda) are out of scope; COMA's train() and the actor-critic
-learner's have their own references on the same gate and the same helpers in tests/coma_ref64.py and tests/a2c_ref.py.
+constants are taken from the oracle. The three opt-in tails are restated the same way: TD(lambda) targets
+(`lambda_returns`: the reference's build_td_lambda_targets recurrence in the run's dtype), the masked Huber loss
+(`td_loss`, differentiated by autograd) and prioritized replay's per-episode importance weights on the loss.
+COMA's train() and the actor-critic learner's have their own references on the same gate and the same helpers in
+tests/coma_ref64.py and tests/a2c_ref.py.
 
 In float64 `ref_step` is the reference. In float32 its error against the float64 run is `e32` for the cases the
 oracle does not cover (the two-layer hypernet, tests/hyper2_ref.py; the feed-forward agent, tests/ffn_ref.py).
@@ -144,8 +147,32 @@ def clip(grads, max_norm, dtype):
     return norm, OrderedDict((k, g * coef) for k, g in grads.items())
 
 
+def lambda_returns(rew, term, mask, y, gamma, lam):
+    """The reference's build_td_lambda_targets, as tests/lambda_oracle.td_lambda_returns states it, in the tensors'
+    own dtype: rew, term, mask (B, L, 1), y = y' (B, L, k), y'[:, t] the target net's value at step t + 1.
+    Returns (targets (B, L, k), bootstrap (B, k) = y'[L-1] (1 - sum_t term))."""
+    lg, og = lam * gamma, (1.0 - lam) * gamma
+    L = y.shape[1]
+    boot = y[:, L - 1] * (1.0 - term.sum(1))
+    ret, out = boot, [None] * L
+    for t in range(L - 1, -1, -1):
+        ret = lg * ret + mask[:, t] * (rew[:, t] + og * y[:, t] * (1.0 - term[:, t]))
+        out[t] = ret
+    return th.stack(out, 1), boot
+
+
+def td_loss(td, m, delta):
+    """The loss term per transition on x = td * m: x^2, or with delta > 0 the Huber form 0.5 x^2 for |x| <= delta,
+    else delta (|x| - 0.5 delta). Returns (term, x)."""
+    x = td * m
+    if delta > 0:
+        ax = x.abs()
+        return th.where(ax <= delta, 0.5 * x * x, delta * (ax - 0.5 * delta)), x
+    return x ** 2, x
+
+
 def ref_step(case, flat_params, flat_targets, batch, dtype=F64, cur_max_override=None, relu_override=None,
-             hid_relu_override=None, hyp_relu_override=None):
+             hid_relu_override=None, hyp_relu_override=None, td_lambda=None, huber_delta=0.0, weights=None):
     """One learner step's loss and its autograd gradient in `dtype`.
 
     The agent is read from the case's parameter names (`rnn.weight_ih`: GRU; `rnn.weight`: feed-forward), the mixer
@@ -153,12 +180,18 @@ def ref_step(case, flat_params, flat_targets, batch, dtype=F64, cur_max_override
     in Case.unflatten's layout; batch: the numpy batch of case.batch(k). cur_max_override (B,T,n) / relu_override
     (B,T+1,n,H): as in OracleQLearner.forward; hid_relu_override (B,T+1,n,H) bool: the feed-forward agent's second
     relu; hyp_relu_override (B,T,2 He) bool: the online two-layer hypernet's layer-1 relu.
+    td_lambda: None for the one-step target, else lambda of `lambda_returns` over the target-side mix y' (per agent
+    without a mixer), lambda and gamma as the C ABI carries them (rounded to f32). huber_delta > 0: `td_loss`'s Huber
+    form (delta rounded to f32 likewise). weights (B,): loss = sum_b w_b sum_t l(td m) / sum m; the other four stats
+    stay unweighted (tests/per_oracle.py).
     Returns a namespace, every array float64 numpy: grads (raw, per named tensor), norm, clipped (per named tensor),
     clipped_flat, loss, stats (the five), hw1 / hwf / hv ((B*T, .), None without a QMixer), a1 ((B,T,2 He), None
     without a two-layer hypernet), pre (fc1 pre-activations, (B,T+1,n,H)), mac_out, target_mac_out (masked, steps
     1..T), masked_q (the Q the target's argmax decision is taken on), cur_max_actions, mask (B,T,1 or n); for the
     feed-forward agent pre2 (its second relu's pre-activations), x1 / hid (both relus' outputs) and
-    target_mac_out_full (unmasked, every step), None for the GRU."""
+    target_mac_out_full (unmasked, every step), None for the GRU; targets and y_next (y', the target-side mix), both
+    (B,T,1 or n); bootstrap ((B,1 or n), None at the one-step target); mtd = td mask (B,T,1 or n) and abs_mtd, its
+    absolute value as (B,T,1), summed over the agents without a mixer."""
     cfg = case.cfg()
     n, gamma = case.n, float(np.float32(cfg["gamma"]))
     flags = (bool(case.obs_last_action), bool(case.obs_agent_id))
@@ -197,12 +230,18 @@ def ref_step(case, flat_params, flat_targets, batch, dtype=F64, cur_max_override
         q_tot, tq_tot = chosen.sum(2, keepdim=True), target_max.sum(2, keepdim=True)
     else:
         q_tot, tq_tot = chosen, target_max
-    targets = rewards + gamma * (1.0 - terminated) * tq_tot
+    boot = None
+    if td_lambda is None:
+        targets = rewards + gamma * (1.0 - terminated) * tq_tot
+    else:
+        targets, boot = lambda_returns(rewards, terminated, mask, tq_tot, gamma, float(np.float32(td_lambda)))
     td = q_tot - targets.detach()
     m = mask.expand_as(td)
-    mtd = td * m
+    ell, mtd = td_loss(td, m, float(np.float32(huber_delta)))
     msum = m.sum()
-    loss = (mtd ** 2).sum() / msum
+    if weights is not None:
+        ell = tt(weights).reshape(B, 1, 1) * ell
+    loss = ell.sum() / msum
     loss.backward()
 
     grads = OrderedDict((k, P[k].grad.double().numpy().copy()) for k in names)
@@ -220,7 +259,9 @@ def ref_step(case, flat_params, flat_targets, batch, dtype=F64, cur_max_override
                            x1=det(th.relu(pre)) if ff else None, hid=det(th.relu(pre2)) if ff else None,
                            mac_out=det(mac_out), a1=None if a1 is None else det(a1).reshape(B, T, -1),
                            target_mac_out=det(tmo), target_mac_out_full=det(tmo_full) if ff else None,
-                           masked_q=det(masked_q), cur_max_actions=cur_max.numpy(), mask=det(m))
+                           masked_q=det(masked_q), cur_max_actions=cur_max.numpy(), mask=det(m),
+                           targets=det(targets), y_next=det(tq_tot), bootstrap=det(boot),
+                           mtd=det(mtd), abs_mtd=det(mtd.abs().sum(2, keepdim=True)))
 
 
 def near_ties(masked_q, mask):
@@ -382,8 +423,25 @@ SHAPES = {
 }                                                         # hold values inside KINK_EPS)
 
 
-def synth_case(shape, mixer="qmix", steps=2):
+# The replay seeds of the TD(lambda) rows (tests/test_gpu_tail_blocks.py): `fast32` and `stream` have an episode of a
+# single transition at the SynthCase default; `base` has none there, 46 is the first seed after it with one beside
+# three episodes of (nearly) full length.
+LAMBDA_SEEDS = {"base": 46, "fast32": 11, "stream": 11}
+
+
+def lambda_case(shape, mixer="qmix", steps=2, data_seed=None):
+    """synth_case for the TD(lambda) rows, a case of its own: one episode has a single transition, and the longest
+    episode's `terminated` flag is cleared (make_replay terminates every episode shorter than T), so that the
+    recurrence's bootstrap y'[L-1] (1 - sum term) is not zero."""
+    case = synth_case(shape, mixer, steps, LAMBDA_SEEDS[shape] if data_seed is None else data_seed)
+    lens = case.data["filled"].sum(1).reshape(-1)
+    assert lens.min() == 2, (shape, lens)
+    case.data["terminated"][int(np.argmax(lens))] = 0
+    return case
+
+
+def synth_case(shape, mixer="qmix", steps=2, data_seed=11):
     from tests.golden_utils import SynthCase
     d = SHAPES[shape]
     return SynthCase("{}_{}".format(shape, mixer), n_episodes=d["B"], steps=steps, mixer=mixer, ragged=True,
-                     min_len=1, **d)
+                     min_len=1, data_seed=data_seed, **d)

@@ -6,6 +6,10 @@
 * the comparer has teeth: kernel-like faults planted in a correct gradient fail the per-block gate, and the global
   `rel(flat) < 1e-4` gate of the teacher-forced tests does not see them.
 * the mixer-kink preconditions (ref64 module docstring) hold for every QMIX shape of tests/test_gpu_grad_blocks.py.
+* ref_step's TD(lambda), Huber and weighted tails against the fp32 oracles of tests/lambda_oracle.py and
+  tests/per_oracle.py in the same bands; their defaults change no bit; six faults a tail kernel could have fail the
+  gate on a named block; every row of tests/test_gpu_tail_blocks.py holds its preconditions with the fp32 oracle
+  standing in for the GPU.
 """
 from collections import OrderedDict
 
@@ -228,3 +232,232 @@ def test_kink_preconditions(synth, shape):
     print(shape, ref64.kink_minima(r))
     ref64.assert_clear_of_kinks(r, c.name)
     assert (r.mask > 0).sum() < r.mask.size   # ragged: dead rows exist and are left out of the minima
+
+
+# ------------------------------------------------------------------ the TD(lambda), Huber and weighted tails of ref_step
+TAIL_CASES = [("base", "qmix"), ("base", "vdn"), ("base", "none"), ("fast32", "qmix"), ("stream", "qmix")]
+TAIL_KINDS = ["lam", "huber", "weights", "all"]
+LAM = 0.8
+
+
+@pytest.fixture(scope="module")
+def lambda_cases():
+    cache = {}
+
+    def get(shape, mixer):
+        if (shape, mixer) not in cache:
+            cache[shape, mixer] = ref64.lambda_case(shape, mixer)
+        return cache[shape, mixer]
+    return get
+
+
+def median_delta(case, nb, lam):
+    """Huber's delta as tests/test_gpu_tail_blocks.py chooses it: the median |td mask| of the live transitions at the
+    case's initial weights, rounded to a multiple of 1/16."""
+    o = OracleQLearner(case.agent_params, case.mixer_params, case.cfg())
+    r = ref64.ref_step(case, o.flat("params"), o.flat("targets"), nb, td_lambda=lam)
+    return round(float(np.median(np.abs(r.mtd)[r.mask > 0])) * 16) / 16
+
+
+def skewed(B):
+    """Weights as the sampler normalises them: the largest is 1, the smallest 1/4."""
+    return np.linspace(0.25, 1.0, B).astype(np.float32)
+
+
+def tail_settings(case, nb, kind):
+    lam = LAM if kind in ("lam", "all") else None
+    delta = median_delta(case, nb, lam) if kind in ("huber", "all") else 0.0
+    w = skewed(nb["obs"].shape[0]) if kind in ("weights", "all") else None
+    return lam, delta, w
+
+
+def per_oracle_raw(case, nb, lam, delta, w):
+    """tests/per_oracle.PEROracleQLearner's unclipped fp32 gradient under the three tails: (oracle, flat, fw, named)."""
+    from tests.per_oracle import PEROracleQLearner
+    o = PEROracleQLearner(case.agent_params, case.mixer_params,
+                          dict(case.cfg(), td_lambda=lam or 0.0, huber_delta=delta))
+    o.weights = w
+    ag, mg, fw = o.gradients(nb)
+    g = OrderedDict(list(ag.items()) + list(mg.items()))
+    return o, np.concatenate([v.ravel() for v in g.values()]), fw, g
+
+
+@pytest.mark.parametrize("kind", TAIL_KINDS)
+@pytest.mark.parametrize("shape,mixer", TAIL_CASES, ids=["_".join(c) for c in TAIL_CASES])
+def test_ref64_tails_match_the_fp32_oracle(lambda_cases, shape, mixer, kind):
+    """ref_step's three tails against the fp32 oracles they share no code with (tests/lambda_oracle.py's recurrence,
+    tests/per_oracle.py's Huber and weights, hand-derived dy), in check_against_oracle's bands."""
+    case = lambda_cases(shape, mixer)
+    nb, _ = case.batch(0)
+    lam, delta, w = tail_settings(case, nb, kind)
+    o, flat, fw, g = per_oracle_raw(case, nb, lam, delta, w)
+    r = ref64.ref_step(case, o.flat("params"), o.flat("targets"), nb, td_lambda=lam, huber_delta=delta, weights=w)
+    errs = ref64.block_errors(flat, r.grads, case)
+    print(case.name, kind, "delta", delta, "worst block", max(errs, key=errs.get), max(errs.values()))
+    for k, e in errs.items():
+        assert e <= 1e-5, (case.name, kind, k, e)
+    m, ms = fw["mask"], float(fw["mask"].sum())
+    st = dict(loss=fw["loss"], grad_norm=clip_grad_norm(OrderedDict(g), case.cfg()["grad_norm_clip"]),
+              td_error_abs=float(np.abs(fw["td"] * m).sum()) / ms,
+              q_taken_mean=float((fw["q_tot"] * m).sum()) / (ms * case.n),
+              target_mean=float((fw["targets"] * m).sum()) / (ms * case.n))
+    for s in STATS:
+        assert abs(st[s] - r.stats[s]) <= 1e-6 * abs(r.stats[s]), (case.name, kind, s, st[s], r.stats[s])
+    live = r.mask > 0
+    k = 1 if mixer != "none" else case.n
+    assert r.targets.shape == r.y_next.shape == r.mtd.shape == r.mask.shape == live.shape[:2] + (k,)
+    assert r.abs_mtd.shape == live.shape[:2] + (1,)
+    assert np.array_equal(r.abs_mtd, np.abs(r.mtd).sum(2, keepdims=True))
+    assert np.abs(fw["targets"] - r.targets)[live].max() <= 1e-6 * np.abs(r.targets[live]).max()
+    if lam:   # the case has what the lambda rows need: a single transition, and a bootstrap that is not zero
+        assert int(nb["filled"].sum(1).min()) == 2 and r.bootstrap.shape == (live.shape[0], k)
+        assert np.abs(r.bootstrap).max() > 1e-3
+    else:
+        assert r.bootstrap is None
+    if delta:
+        below = float((np.abs(r.mtd)[live] <= delta).mean())
+        assert 0.4 <= below <= 0.6, (case.name, kind, below)   # delta is the median: both regimes carry the loss
+    # the tail was taken, not ignored
+    plain = ref64.ref_step(case, o.flat("params"), o.flat("targets"), nb)
+    assert rel_err(r.clipped_flat, plain.clipped_flat) > 1e-2
+
+
+@pytest.mark.parametrize("shape,mixer", [("base", "qmix"), ("base", "none")])
+def test_tail_defaults_are_bitwise(synth, shape, mixer):
+    """The new keyword arguments at their defaults, and weights == 1, change no bit of the step."""
+    c = ref64.synth_case(shape, mixer) if mixer != "qmix" else synth(shape)
+    nb, _ = c.batch(0)
+    flat = ref64.flat_of(c)
+    a = ref64.ref_step(c, flat, flat, nb)
+    b = ref64.ref_step(c, flat, flat, nb, td_lambda=None, huber_delta=0.0, weights=None)
+    ones = ref64.ref_step(c, flat, flat, nb, weights=np.ones(nb["obs"].shape[0], np.float32))
+    for other in (b, ones):
+        assert other.loss == a.loss and other.stats == a.stats and other.norm == a.norm
+        for k in a.grads:
+            assert np.array_equal(other.grads[k], a.grads[k]), k
+        assert np.array_equal(other.clipped_flat, a.clipped_flat)
+
+
+def _shifted_returns(rew, term, mask, y, gamma, lam):
+    """lambda_returns reading y'[t + 1] where y'[t] belongs (the last step reads its own)."""
+    import torch as th
+    L = y.shape[1]
+    return _LAMBDA_RETURNS(rew, term, mask, th.cat([y[:, 1:], y[:, L - 1:]], 1), gamma, lam)[0], \
+        y[:, L - 1] * (1.0 - term.sum(1))
+
+
+def _no_bootstrap_returns(rew, term, mask, y, gamma, lam):
+    """lambda_returns started from 0 where y'[L-1] (1 - sum term) belongs. The recurrence is linear in its start:
+    step t carries (lambda gamma)^(L - t) of it."""
+    import torch as th
+    full, boot = _LAMBDA_RETURNS(rew, term, mask, y, gamma, lam)
+    L = y.shape[1]
+    decay = th.tensor([(lam * gamma) ** (L - t) for t in range(L)], dtype=y.dtype).reshape(1, L, 1)
+    return full - decay * boot.unsqueeze(1), boot
+
+
+def _unmasked_huber(td, m, delta):
+    """td_loss with Huber on td where td * m belongs: the padded transitions reach the loss and dy."""
+    import torch as th
+    return _TD_LOSS(td, th.ones_like(m), delta)[0], td * m
+
+
+_LAMBDA_RETURNS, _TD_LOSS = ref64.lambda_returns, ref64.td_loss
+
+# (name, blind, which reference function is replaced, by what, keyword arguments of the mutant's ref_step that differ
+# from the reference's, the block named). The reference runs lambda = 0.8, Huber at the median and skewed weights
+# together. blind: the old gate, rel(flat) < 1e-4, is asserted not to see the mutant. None of these six is small on
+# the global max once its tail is really on (the figures are printed), so none is blind in that sense; the gap they
+# stood in is one of coverage. Off the fast16 shapes the old tests ran PER at beta = 0 only, where W == 1: there the
+# two PER mutants leave every bit of the gradient as it is (asserted below), and Huber met a reference on fast16 alone.
+TAIL_MUTANTS = [
+    ("w on the loss, not on dy", False, None, None, dict(weights=None), "V.0.weight"),
+    ("w[b] of the neighbouring episode", False, None, None, dict(weights="roll"), "hyper_w_1.bias[agent1]"),
+    ("lambda recurrence reads y'[t+1]", False, "lambda_returns", _shifted_returns, {}, "fc1.weight[agent_id]"),
+    ("bootstrap term dropped", False, "lambda_returns", _no_bootstrap_returns, {}, "rnn.bias_hh[z]"),
+    ("Huber clamps at 2 delta", False, None, None, dict(huber_delta="double"), "hyper_w_final.bias"),
+    ("Huber's dy without the mask", False, "td_loss", _unmasked_huber, {}, "fc2.bias"),
+]
+
+
+@pytest.fixture(scope="module")
+def tail_gradients(lambda_cases):
+    c = lambda_cases("base", "qmix")
+    nb, _ = c.batch(0)
+    lam, delta, w = tail_settings(c, nb, "all")
+    o, flat, fw, _ = per_oracle_raw(c, nb, lam, delta, w)
+    r = ref64.ref_step(c, o.flat("params"), o.flat("targets"), nb, td_lambda=lam, huber_delta=delta, weights=w)
+    return c, nb, o, dict(td_lambda=lam, huber_delta=delta, weights=w), r, ref64.block_errors(flat, r.grads, c)
+
+
+def test_unmodified_tail_gradient_passes_the_gate(tail_gradients):
+    c, nb, o, kw, r, e32 = tail_gradients
+    assert not ref64.failures(e32, ref64.tolerances(e32))
+    assert max(e32.values()) < 1e-6
+
+
+@pytest.mark.parametrize("what,blind,target,repl,diff,block", TAIL_MUTANTS, ids=[m[0] for m in TAIL_MUTANTS])
+def test_gate_catches_tail_mutant(tail_gradients, monkeypatch, what, blind, target, repl, diff, block):
+    c, nb, o, kw, r, e32 = tail_gradients
+    kw2 = dict(kw)
+    for k, v in diff.items():
+        kw2[k] = np.roll(kw[k], 1) if v == "roll" else 2.0 * kw[k] if v == "double" else v
+    if target:
+        monkeypatch.setattr(ref64, target, repl)
+    mut = ref64.ref_step(c, o.flat("params"), o.flat("targets"), nb, **kw2)
+    monkeypatch.undo()
+    got = np.concatenate([g.ravel() for g in mut.grads.values()])
+    bad = ref64.failures(ref64.block_errors(got, r.grads, c), ref64.tolerances(e32))
+    assert block in bad, (what, bad)
+    old = rel_err(got, np.concatenate([g.ravel() for g in r.grads.values()]))
+    print(what, "per-block", bad[block], "blocks over", len(bad), "of", len(e32), "old global rel", old)
+    assert (old < OLD_GATE) == blind, (what, old)
+    if "weights" in diff:   # what the old tests gave every kernel but fast16: W == 1, and the mutant is the reference
+        one = dict(kw, weights=np.ones_like(kw["weights"]))
+        a = ref64.ref_step(c, o.flat("params"), o.flat("targets"), nb, **one)
+        b = ref64.ref_step(c, o.flat("params"), o.flat("targets"), nb, **dict(one, weights=None))
+        assert rel_err(b.clipped_flat, a.clipped_flat) == 0.0 < OLD_GATE
+
+
+def test_tail_rows_hold_their_preconditions():
+    """Every row of tests/test_gpu_tail_blocks.py on the CPU, the fp32 oracle standing in for the GPU over both steps:
+    the draw of a PER row has its two weights and the episodes a lambda row needs; delta is the step-0 median; both
+    Huber regimes are live; the bootstrap is not zero; the QMIX rows keep clear of the mixer's kinks."""
+    from tests import reward_norm_ref as RN
+    from tests import test_gpu_tail_blocks as TB
+    from tests.per_oracle import PEROracleQLearner
+    from tests.test_gpu_epymarl_keys import with_rewards
+    from tests.test_gpu_per import numpy_batch
+    assert len(TB.ROWS) == 28 and set(TB.HUBER_DELTA) == {r for r, v in TB.ROWS.items() if TB.TAILS[v[3]][2]}
+    cases = {}
+    for row, (shape, mixer, switches, tail, mix) in TB.ROWS.items():
+        lam, per, hub, rs, want = TB.TAILS[tail]
+        case = cases.setdefault(TB.case_key(row), TB.tail_case(row))
+        assert case.n_episodes == case.B and case.T == ref64.SHAPES[shape]["T"]
+        delta = TB.HUBER_DELTA[row] if hub else 0.0
+        if hub:
+            assert delta == median_delta(case, case.batch(0)[0], LAM if lam else None), row
+            assert np.float32(delta) == delta
+        o = PEROracleQLearner(case.agent_params, case.mixer_params,
+                              dict(case.cfg(), td_lambda=TB.LAM if lam else 0.0, huber_delta=delta))
+        need = TB.lambda_needs(case) if lam else ()
+        state = RN.INIT
+        for k in range(2):
+            w = None
+            if per:
+                prio, u, ids, w = TB.per_draw(case, k, need)
+                assert prio.max() >= 0.5 * prio.sum() and len(set(w.tolist())) >= 2 and set(need) <= set(ids)
+                assert np.array_equal(u * 256, np.round(u * 256))
+                nb = numpy_batch(case, ids, int(case.data["filled"].sum(1).max()))
+            else:
+                nb, _ = case.batch(k)
+            if rs:
+                state, r8 = RN.standardise(state, nb["reward"][:, :-1])
+                nb = with_rewards(nb, r8.astype(np.float32))
+            o.weights = w
+            ref = ref64.ref_step(case, o.flat("params"), o.flat("targets"), nb, weights=w,
+                                 td_lambda=TB.LAM if lam else None, huber_delta=delta)
+            if mixer == "qmix":
+                ref64.assert_clear_of_kinks(ref, "{} step {}".format(row, k))
+            TB.preconditions(ref, nb, lam, delta, "{} step {}".format(row, k))
+            o.train(nb, 1000 * k, case.episodes[k])
