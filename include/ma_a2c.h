@@ -6,7 +6,8 @@
  * the given HIP stream, int status + mq_last_error().
  *
  * The critic is a V network, fc1 (K -> Hc) relu fc2 (Hc -> Hc) relu fc3 (Hc -> 1), trained in ONE optimiser step over
- * every t of the batch against n-step returns of the target critic; the actor is the GRU agent with a softmax policy
+ * every t of the batch against n-step returns of the target critic; the actor is the GRU agent, or with
+ * ma_config.agent = MQ_AGENT_FFN the feed-forward one (epymarl's use_rnn: False), with a softmax policy
  * (no epsilon floor), trained with the advantage td = (return - V) mask and an entropy bonus. Both optimisers are
  * RMSprop (the reference's) or, after ma_set_adam, torch.optim.Adam.
  */
@@ -44,6 +45,7 @@ typedef struct ma_config {
   float lr, optim_alpha, optim_eps, grad_norm_clip;   /* one lr for both optimisers */
   const float* gamma_pow;          /* HOST pointer, q_nstep + 2 floats: g[k] = float32(gamma ** k); ma_create copies it */
   int32_t max_batch, max_seq;
+  int32_t agent;                   /* MQ_AGENT_*: 0 (a zeroed field) the GRU agent, MQ_AGENT_FFN the feed-forward one */
 } ma_config;
 
 /* Adam in RMSprop's place for both optimisers: the first-moment buffers [Pa] / [Pc] (the second moments live where
@@ -83,18 +85,29 @@ typedef struct ma_plan {
   int32_t policy_lanes;   /* n_actions: the live lanes of each of its waves (of 64) */
   int32_t ap;             /* dlogits' row pitch: n_actions rounded up to 4 (pad columns written as zeros) */
   int32_t ns_aw1, ns_aw2; /* split-K slices of the agent's dW1 and dW2 */
-  int32_t bwd_blocks;     /* the BPTT's workgroups */
+  int32_t bwd_blocks;     /* the BPTT's workgroups; feed-forward actor: ffn_actor_bwd_kernel's (= ffn_blocks) */
   int32_t reward_norm;    /* 1: the step standardised its rewards */
   int32_t adam;           /* 1: Adam applied, 0: RMSprop */
   int32_t epochs;         /* optimisation epochs the step ran: 1, or ma_ppo.epochs */
   int32_t hoisted;        /* PPO: launches and copies made once per step, not once per epoch (0: not a PPO step) */
 } ma_plan;
 
+/* What the last ma_train_step launched for its actor (ma_last_actor): a struct of its own, so ma_plan keeps its
+ * size and callers built against it need no rebuild. */
+typedef struct ma_actor {
+  int32_t agent;          /* MQ_AGENT_*; the items below are 0 with the GRU agent */
+  int32_t ffn_tiles;      /* 64-row tiles of the actor's rows */
+  int32_t ffn_blocks;     /* ffn_actor_bwd_kernel's workgroups = its slabs (MQ_PLAN ffn_actor_blocks=<n> lowers the cap) */
+  int32_t ffn_tiles_per_block;   /* tiles each of them walks, in order (the last one the rest) */
+  int32_t ffn_fwd_lds;    /* ffn_actor_fwd_kernel's dynamic LDS, bytes: 87040 when W1 is streamed in K chunks */
+} ma_actor;
+
 typedef struct ma_handle ma_handle;
 
 int ma_create(const ma_config* cfg, ma_handle** out);
 int ma_destroy(ma_handle* h);
-/* agent_offsets[MQ_P_COUNT + 1] (RNNAgent layout, mixer entries empty), critic_offsets[MA_P_COUNT + 1]. */
+/* agent_offsets[MQ_P_COUNT + 1] (RNNAgent layout, mixer entries empty; feed-forward: rnn.weight / rnn.bias at
+ * MQ_P_FFN_W / MQ_P_FFN_B, the GRU's four empty), critic_offsets[MA_P_COUNT + 1]. */
 int ma_param_offsets(const ma_handle* h, int64_t* agent_offsets, int64_t* critic_offsets);
 /* agent / agent_sq: [Pa]; agent_grad: [Pa + MQ_NSUMS]; critic / target_critic / critic_sq: [Pc];
  * critic_grad: [Pc + MA_NTAIL]; stats: [MA_NSTATS]. Both clipped gradients are left in the grad buffers. */
@@ -126,6 +139,7 @@ int ma_critic_forward(const float* critic, const ma_config* cfg, const mq_replay
  * 6 = the last epoch's ratio [T][B*n]. */
 int ma_copy_intermediate(ma_handle* h, int which, float* dst, int64_t* count, void* stream);
 int ma_last_plan(const ma_handle* h, ma_plan* out);
+int ma_last_actor(const ma_handle* h, ma_actor* out);
 
 #ifdef __cplusplus
 }

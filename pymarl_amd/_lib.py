@@ -46,7 +46,7 @@ EXPORTS = [
 MA_EXPORTS = [
     "ma_create", "ma_destroy", "ma_param_offsets", "ma_bind", "ma_set_adam", "ma_set_reward_norm", "ma_train_step",
     "ma_update_targets", "ma_critic_forward_workspace", "ma_critic_forward", "ma_copy_intermediate", "ma_last_plan",
-    "ma_set_ppo",
+    "ma_set_ppo", "ma_last_actor",
 ]
 
 # mc_allreduce_fn (include/mc_coma.h): int (*)(float* buf, int64_t count, void* stream, void* ctx)
@@ -116,6 +116,7 @@ class MAConfig(ctypes.Structure):
         ("entropy_coef", ctypes.c_float), ("lr", ctypes.c_float), ("optim_alpha", ctypes.c_float),
         ("optim_eps", ctypes.c_float), ("grad_norm_clip", ctypes.c_float), ("gamma_pow", ctypes.c_void_p),
         ("max_batch", ctypes.c_int32), ("max_seq", ctypes.c_int32),
+        ("agent", ctypes.c_int32),   # AGENT_GRU (0, a zeroed field) or AGENT_FFN: the feed-forward actor
     ]
 
 
@@ -138,6 +139,15 @@ class MAPlan(ctypes.Structure):
         "rows", "rows_target", "k", "kp", "hidden", "vec16", "fwd_tiles", "vhead_blocks", "nstep_lds", "dv_blocks",
         "ns_cw2", "ns_cw1", "policy_blocks", "policy_tail", "policy_lanes", "ap", "ns_aw1", "ns_aw2", "bwd_blocks", "reward_norm", "adam",
         "epochs", "hoisted")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class MAActor(ctypes.Structure):
+    """ma_actor: what the last step launched for its actor; all 0 with the GRU agent."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("agent", "ffn_tiles", "ffn_blocks", "ffn_tiles_per_block",
+                                               "ffn_fwd_lds")]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -262,6 +272,7 @@ def load(required=True):
         "ma_critic_forward": ([vp, ctypes.POINTER(MAConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp], ctypes.c_int),
         "ma_copy_intermediate": ([vp, ctypes.c_int, vp, ctypes.POINTER(i64), vp], ctypes.c_int),
         "ma_last_plan": ([vp, ctypes.POINTER(MAPlan)], ctypes.c_int),
+        "ma_last_actor": ([vp, ctypes.POINTER(MAActor)], ctypes.c_int),
         "ma_set_ppo": ([vp, ctypes.POINTER(MAPpo)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():

@@ -6,7 +6,8 @@ step's `h = relu(rnn(x1))`, which the next step does not read.
 `forward(ep_batch, t)` is one fused HIP step (`mq_mac_forward`): it builds [obs_t | onehot(a_{t-1}) | onehot(id)]
 from the replay rows in-kernel (basic_controller.py:100-135) and runs fc1 -> GRUCell -> fc2 for every
 (episode, agent) row. For agent_output_type "pi_logits" (COMA) a second HIP kernel (`mc_policy`) applies the
-reference's -1e10 mask, softmax and epsilon floor in place (basic_controller.py:53-73).
+reference's -1e10 mask, softmax and epsilon floor in place (basic_controller.py:53-73); the actor-critic and PPO
+learners' MAC takes either agent there, COMA's the GRU agent only.
 
 A host-resident batch (the reference ParallelRunner's batch under buffer_cpu_only, parallel_runner.py:45) is read
 the reference's way: the step's rows go to the device first (basic_controller.py:105-115, `.to(self.args.device)`),
@@ -34,9 +35,8 @@ class BasicMAC:
         input_shape = self._get_input_shape(scheme)
         self._build_agents(input_shape)
         self.agent_output_type = args.agent_output_type
-        if self.agent_output_type == "pi_logits" and not use_rnn_config(args):
-            raise ValueError("use_rnn: False is not supported with agent_output_type pi_logits (COMA's policy, "
-                             "mc_policy): COMA's actor is the GRU agent")
+        if not use_rnn_config(args) and getattr(args, "learner", None) == "coma_learner":
+            raise ValueError("use_rnn: False is not supported with learner coma_learner: COMA's actor is the GRU agent")
         self.action_selector = action_REGISTRY[args.action_selector](args)
         self.hidden_states = None
 

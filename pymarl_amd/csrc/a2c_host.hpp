@@ -28,6 +28,9 @@ struct ma_handle {
   int* halt;
   // actor workspace
   float *dL, *dHo, *pi, *ppart, *slab_fc2, *red_tmp, *norm_part;
+  float* slab_ffn;   // [ffn_slabs_max][len_rnn] the feed-forward actor's [dWr | dbr | dW2 | db2] slabs
+  int ffn_slabs_max = 0, ffn_cap = 0;   // slabs slab_ffn holds; MQ_PLAN ffn_actor_blocks (0: the default cap)
+  bool ffn_attr = false;   // the two ffn_actor kernels' dynamic-LDS attributes are raised
   float *old_lp, *ratio;   // [T R] each, PPO: epoch 0's log-probabilities of the taken actions, the last epoch's ratio
   float* gbak;   // [Pa + MQ_NSUMS | Pc + MA_NTAIL] both gradient buffers before the reductions (a2c_gate_kernel)
   double* rbak;  // [3] the running reward statistics before reward_norm_kernel merged the batch into them
@@ -38,6 +41,7 @@ struct ma_handle {
   bool ppo = false;   // ma_set_ppo: ma_train_step runs pp.epochs epochs (ppo_host.hpp)
   ma_ppo pp{};
   ma_plan last{};
+  ma_actor last_ffn{};
   int last_T = 0, last_R = 0;
 
   ~ma_handle() { mq_destroy(ah); }   // the buffers free themselves
@@ -52,6 +56,8 @@ int ma_check_config(const ma_config& c, bool train) {
   if (c.n_agents < 1 || c.n_agents > 64) return set_err(MQ_ERR_ARG, "n_agents must be in [1, 64]");
   if (c.n_actions < 1 || c.n_actions > 64) return set_err(MQ_ERR_ARG, "n_actions must be in [1, 64]");
   if (c.obs_dim < 1 || c.state_dim < 1) return set_err(MQ_ERR_ARG, "obs_dim / state_dim must be positive");
+  if (c.agent != MQ_AGENT_GRU && c.agent != MQ_AGENT_FFN)
+    return set_err(MQ_ERR_ARG, "agent must be MQ_AGENT_GRU (0) or MQ_AGENT_FFN (1)");
   if (!train) return MQ_OK;
   if (c.q_nstep < 1) return set_err(MQ_ERR_ARG, "q_nstep must be >= 1");
   if (!(c.entropy_coef >= 0.0f)) return set_err(MQ_ERR_ARG, "entropy_coef must be >= 0");
@@ -168,11 +174,25 @@ int ma_returns(const ma_handle* h, const ADims& cd, const Rep& rp, const ma_plan
 }
 
 // The step's plan and its actor's, checked against what ma_create allocated (max_batch / max_seq bound the slabs, and
-// PPO's old_lp and ratio) and against the n-step pass's LDS.
-int ma_step_plan(const ma_handle* h, int B, int Tp, ma_plan* pl, ActorPlan* ap) {
-  *pl = a2c_plan(h->cfg, B, Tp, h->rew_state != nullptr, h->adam, ap);
-  if (pl->ns_cw1 > h->ns_max || pl->ns_cw2 > h->ns_max || pl->dv_blocks > h->ndv_max || ap->ns_w2 > kNsplitMax)
+// PPO's old_lp and ratio; the feed-forward actor's slabs) and against the n-step pass's and the feed-forward forward's
+// LDS. The feed-forward kernels' dynamic LDS is past a launch's default: their attributes are raised once per handle.
+int ma_step_plan(ma_handle* h, int B, int Tp, ma_plan* pl, ActorPlan* ap) {
+  *pl = a2c_plan(h->cfg, B, Tp, h->rew_state != nullptr, h->adam, ap, h->ffn_cap);
+  if (pl->ns_cw1 > h->ns_max || pl->ns_cw2 > h->ns_max || pl->dv_blocks > h->ndv_max || ap->ns_w2 > kNsplitMax ||
+      ap->ffn_blocks > h->ffn_slabs_max)
     return set_err(MQ_ERR_STATE, "actor-critic plan exceeds the workspace");
+  if (ap->agent == MQ_AGENT_FFN) {
+    if (ap->ffn_fwd_lds > kFfnActorLdsMax) return set_err(MQ_ERR_ARG, "the feed-forward actor's forward exceeds the LDS");
+    MQ_LDS(ffn_actor_fwd_kernel, ap->ffn_fwd_lds);
+    MQ_LDS(ffn_actor_bwd_kernel, kFfnActorBwdLds);
+    if (!h->ffn_attr) {
+      MQ_HIP(hipFuncSetAttribute((const void*)ffn_actor_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)kFfnActorLdsMax));
+      MQ_HIP(hipFuncSetAttribute((const void*)ffn_actor_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)kFfnActorLdsMax));
+      h->ffn_attr = true;
+    }
+  }
   if (a2c_nstep_lds_bytes(Tp, h->cfg.n_agents) > kA2cNstepLdsMax)
     return set_err(MQ_ERR_ARG, "episode too long for the LDS n-step return pass");
   return MQ_OK;
@@ -248,7 +268,7 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
   int rc = ma_check_config(c, true);
   if (rc) return rc;
   if (c.max_batch * c.n_agents > MQ_INLINE_IDS * 64) return set_err(MQ_ERR_ARG, "max_batch * n_agents too large");
-  const mq_config ac = agent_config(c, c.gamma_pow[1]);   // (ma_check_config: gamma_pow is not NULL)
+  const mq_config ac = agent_config(c, c.gamma_pow[1], c.agent);   // (ma_check_config: gamma_pow is not NULL)
   mq_handle* ah = nullptr;
   if ((rc = mq_create(&ac, &ah))) return rc;
   std::unique_ptr<ma_handle> h(new ma_handle());   // owns ah from here: a failure below frees both
@@ -268,6 +288,9 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
   const int64_t Tp = c.max_seq, R = (int64_t)c.max_batch * n, T = Tp - 1, RT = T * R;
   h->ns_max = a2c_ns_max(RT);
   h->ndv_max = (int)((RT + A2C_DV_ROWS - 1) / A2C_DV_ROWS);
+  const bool ffn = c.agent == MQ_AGENT_FFN;
+  h->ffn_slabs_max = ffn ? ffn_actor_blocks_max(RT) : 0;
+  h->ffn_cap = plan_int("ffn_actor_blocks", 0);   // the one read of this MQ_PLAN item per handle
   const int64_t lw1 = (int64_t)Hc * h->K + Hc, lw2 = (int64_t)Hc * Hc + Hc, lw3 = Hc + 1;
   const int64_t cred_tmp = kRedZ * (lw1 + lw2 + lw3 + 8);
   const int64_t red_tmp = kRedZ * ((int64_t)mq::H * ah->I + mq::H) + kRedZ * ah->len_rnn + kRedZ * (A * mq::H + A) +
@@ -288,6 +311,7 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
       {"dL", RT * h->Ap, &h->dL}, {"dHo", RT * mq::H, &h->dHo}, {"pi", RT * A, &h->pi},
       {"ppart", ((RT + 3) / 4) * 8, &h->ppart},
       {"slab_fc2", (int64_t)kNsplitMax * (A * mq::H + A), &h->slab_fc2},
+      {"slab_ffn", h->ffn_slabs_max * ah->len_rnn, &h->slab_ffn},
       {"red_tmp", red_tmp, &h->red_tmp},
       {"norm_part", kNormPartMax, &h->norm_part},
       {"old_lp", RT, &h->old_lp}, {"ratio", RT, &h->ratio},
@@ -420,10 +444,11 @@ int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void*
   if ((rc = ma_critic_reduce(h, pl, s, &nnorm_c))) return rc;
   // ---- actor backward (the COMA learner's chain)
   int nnorm_a;
-  if ((rc = actor_backward(h, ap, d, rp, L, w, RT, pl.policy_blocks, s, &nnorm_a))) return rc;
+  if ((rc = actor_backward(h, ap, d, rp, L, w, RT, pl.policy_blocks, s, &nnorm_a, h->slab_ffn))) return rc;
   // ---- both applies after both backwards; an empty batch (M = 0) halts both
   if ((rc = ma_gate_apply(h, nnorm_c, nnorm_a, adam_step, s))) return rc;
   h->last = pl;
+  h->last_ffn = a2c_actor_report(ap);
   h->last_T = T;
   h->last_R = R;
   return MQ_OK;
@@ -468,6 +493,13 @@ int ma_last_plan(const ma_handle* h, ma_plan* out) {
   if (!h || !out) return set_err(MQ_ERR_ARG, "NULL argument");
   if (h->last_T <= 0) return set_err(MQ_ERR_STATE, "no actor-critic train step has run");
   *out = h->last;
+  return MQ_OK;
+}
+
+int ma_last_actor(const ma_handle* h, ma_actor* out) {
+  if (!h || !out) return set_err(MQ_ERR_ARG, "NULL argument");
+  if (h->last_T <= 0) return set_err(MQ_ERR_STATE, "no actor-critic train step has run");
+  *out = h->last_ffn;
   return MQ_OK;
 }
 

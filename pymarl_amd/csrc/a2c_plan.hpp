@@ -22,8 +22,10 @@ inline size_t a2c_nstep_lds_bytes(int Tp, int n) { return (size_t)Tp * (n + 2) *
 // ever rounds this number down).
 inline int a2c_ns_max(int64_t RTmax) { return (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RTmax / 256)); }
 
-// `actor`, when given, receives the ActorPlan the actor's launches read: ns_aw1 / ns_aw2 / bwd_blocks report it.
-inline ma_plan a2c_plan(const ma_config& c, int B, int t_len, bool reward_norm, bool adam, ActorPlan* actor = nullptr) {
+// `actor`, when given, receives the ActorPlan the actor's launches read: ns_aw1 / ns_aw2 / bwd_blocks and the ffn_*
+// items (a2c_actor_report) report it. ffn_cap: MQ_PLAN ffn_actor_blocks (actor_plan.hpp).
+inline ma_plan a2c_plan(const ma_config& c, int B, int t_len, bool reward_norm, bool adam, ActorPlan* actor = nullptr,
+                        int ffn_cap = 0) {
   ma_plan p{};
   const int R = B * c.n_agents, T = t_len - 1;
   const int64_t RT = (int64_t)T * R;
@@ -44,14 +46,19 @@ inline ma_plan a2c_plan(const ma_config& c, int B, int t_len, bool reward_norm, 
   p.policy_lanes = c.n_actions;
   p.ap = (c.n_actions + 3) & ~3;
   const int I = c.obs_dim + (c.obs_last_action ? c.n_actions : 0) + (c.obs_agent_id ? c.n_agents : 0);
-  const ActorPlan ap = actor_plan(I, c.obs_dim, c.n_actions, c.n_agents, R, RT);
+  const ActorPlan ap = actor_plan(I, c.obs_dim, c.n_actions, c.n_agents, R, RT, c.agent, ffn_cap);
   if (actor) *actor = ap;
   p.ns_aw1 = ap.ns_w1;
   p.ns_aw2 = ap.ns_w2;
-  p.bwd_blocks = ap.nblk_bwd;
+  p.bwd_blocks = c.agent == MQ_AGENT_FFN ? ap.ffn_blocks : ap.nblk_bwd;
   p.reward_norm = reward_norm ? 1 : 0;
   p.adam = adam ? 1 : 0;
   return p;
+}
+
+// What ma_last_actor reports of an ActorPlan.
+inline ma_actor a2c_actor_report(const ActorPlan& ap) {
+  return ma_actor{ap.agent, ap.ffn_tiles, ap.ffn_blocks, ap.ffn_tpb, (int32_t)ap.ffn_fwd_lds};
 }
 
 }  // namespace mq

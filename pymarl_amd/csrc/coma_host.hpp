@@ -97,15 +97,16 @@ mq_replay shard_replay(const mc_config& c, const mq_replay& b, int lo, int hi) {
   return s;
 }
 
-// The internal agent handle's config (no mixer) from a COMA or an actor-critic config `c`.
+// The internal agent handle's config (no mixer) from a COMA or an actor-critic config `c`; `agent`: MQ_AGENT_*.
 template <class C>
-mq_config agent_config(const C& c, float gamma) {
+mq_config agent_config(const C& c, float gamma, int agent = MQ_AGENT_GRU) {
   mq_config a{};
   a.n_agents = c.n_agents; a.n_actions = c.n_actions; a.obs_dim = c.obs_dim; a.state_dim = c.state_dim;
   a.rnn_hidden_dim = c.rnn_hidden_dim; a.mixer = MQ_MIXER_NONE;
   a.obs_last_action = c.obs_last_action; a.obs_agent_id = c.obs_agent_id; a.gamma = gamma; a.lr = c.lr;
   a.optim_alpha = c.optim_alpha; a.optim_eps = c.optim_eps; a.grad_norm_clip = c.grad_norm_clip;
   a.max_batch = c.max_batch; a.max_seq = c.max_seq;
+  a.agent = agent;
   return a;
 }
 
@@ -113,12 +114,21 @@ mq_config agent_config(const C& c, float gamma) {
 // its agent handle h->ah lends the workspace `w` (w.dHo the learner's), h->agent are the agent's parameters, RT = T R
 // the actor's rows. Which kernels and how many slices is ActorPlan's answer (actor_plan.hpp).
 //
-// The agent unroll over t < T, online net only: the logits land in w.Q.
+// The agent unroll over t < T, online net only: the logits land in w.Q. The feed-forward actor is one launch
+// (ffn_actor_fwd_kernel: X1, Hh = w.Hs, the logits and XIN).
 template <class Hd>
 int actor_forward(const Hd* h, const ActorPlan& ap, const Dims& d, const Rep& rpa, const Lay& L, const Work& w,
                   int64_t RT, hipStream_t st) {
   const mq_handle* ah = h->ah;
   const float* Pa = h->agent;
+  if (ap.agent == MQ_AGENT_FFN) {
+    const FfnActorFwd p{d, rpa, Pa, ah->off[MQ_P_FC1_W], ah->off[MQ_P_FC1_B], ah->off[MQ_P_FFN_W], ah->off[MQ_P_FFN_B],
+                        ah->off[MQ_P_FC2_W], ah->off[MQ_P_FC2_B], w.X1, w.Hs, w.Q, w.XIN, RT, ap.ffn_tiles,
+                        ap.ffn_resident};
+    hipLaunchKernelGGL(ffn_actor_fwd_kernel, dim3(ap.ffn_fwd_blocks), dim3(256), ap.ffn_fwd_lds, st, p);
+    MQ_HIP(hipGetLastError());
+    return MQ_OK;
+  }
   if (ap.fused_fwd) {
     launch_fwd_fused(dim3(d.R, 1), st, d, rpa, Pa, Pa, L, w);
     MQ_HIP(hipGetLastError());
@@ -141,13 +151,27 @@ int actor_forward(const Hd* h, const ActorPlan& ap, const Dims& d, const Rep& rp
 
 // From the policy kernel's h->dL [RT][Ap] (dense dLoss/dlogits) and its npol blocks of loss sums h->ppart: BPTT with
 // the dense output gradient, the split-K weight gradients, and the two-pass reduction into h->agrad [Pa | MQ_NSUMS];
-// *nnorm = the norm partials it left in h->norm_part.
+// *nnorm = the norm partials it left in h->norm_part. The feed-forward actor: ffn_actor_bwd_kernel (dP1 and one
+// [dWr | dbr | dW2 | db2] slab per workgroup into ffn_slab, the learner's), the split-K [dW1 | db1], the reduction.
 template <class Hd>
 int actor_backward(const Hd* h, const ActorPlan& ap, const Dims& d, const Rep& rpa, const Lay& L, const Work& w,
-                   int64_t RT, int npol, hipStream_t s, int* nnorm) {
+                   int64_t RT, int npol, hipStream_t s, int* nnorm, float* ffn_slab = nullptr) {
   const mq_handle* ah = h->ah;
   const float* Pa = h->agent;
   const int A = d.A;
+  if (ap.agent == MQ_AGENT_FFN) {
+    const FfnActorBwd p{h->dL, h->Ap, A, Pa + ah->off[MQ_P_FC2_W], Pa + ah->off[MQ_P_FFN_W], w.Hs, w.X1, w.dP1,
+                        ffn_slab, ah->len_rnn, RT, ap.ffn_tiles, ap.ffn_tpb};
+    hipLaunchKernelGGL(ffn_actor_bwd_kernel, dim3(ap.ffn_blocks), dim3(256), kFfnActorBwdLds, s, p);
+    MQ_HIP(hipGetLastError());
+    Dw1Prob p1{d.I, w.dP1, w.XIN, w.slab_fc1, RT, ap.ns_w1};
+    MQ_HIP(launch_gemm(p1, mq::H, d.I, ap.ns_w1, s));
+    RedBuilder rb(h->red_tmp);
+    rb.add(w.slab_fc1, ap.ns_w1, (int64_t)mq::H * d.I + mq::H, h->agrad + ah->off[MQ_P_FC1_W], true);
+    rb.add(ffn_slab, ap.ffn_blocks, ah->len_rnn, h->agrad + ah->off[MQ_P_FFN_W], true);
+    rb.add(h->ppart, npol, MQ_NSUMS, h->agrad + h->Pa, false);
+    return launch_reduce(rb, h->norm_part, "agent", s, nnorm);
+  }
   {
     DhoProb p{h->dL, h->Ap, A, Pa + ah->off[MQ_P_FC2_W], w.dHo, RT};
     MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));

@@ -21,7 +21,8 @@
 //   apply    / sum(mask), clip_grad_norm_, RMSprop (mq_set_adam: Adam, apply_adam_kernel)
 // The feed-forward agent (mq_config.agent = MQ_AGENT_FFN, ffn_kernels.hpp) has no recurrence: fc1 / rnn / fc2 are three
 // GEMMs forward (gi and gru_fwd are absent), and gru_bwd's place is taken by ffn_dp2_kernel (dP2 and the fc2 gradients),
-// dx1 by the dP1 GEMM, dw1 by [dW_rnn | db_rnn] and dW1; everything from `hyper` to `apply` is untouched.
+// dx1 by the dP1 GEMM, dw1 by [dW_rnn | db_rnn] and dW1; everything from `hyper` to `apply` is untouched. (The
+// actor-critic and PPO learners run that agent as two fused launches of their own: ffn_actor_kernels.hpp.)
 //            (soft target updates, mq_set_soft_target: soft_update_kernel as the step's last launch)
 // Reward standardisation (mq_set_reward_norm): reward_norm_kernel ahead of `mix`, whose one-step pass and TD(lambda)
 // scan then read its output in place of the storage's rewards (epymarl_kernels.hpp).

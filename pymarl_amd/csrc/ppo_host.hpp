@@ -71,7 +71,7 @@ int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStr
     // ---- both backwards, then both applies (Adam step number adam_step + k), then the epoch's stats row
     int nnorm_c, nnorm_a;
     if ((rc = ma_critic_dw(h, pl, RT, s)) || (rc = ma_critic_reduce(h, pl, s, &nnorm_c)) ||
-        (rc = actor_backward(h, ap, d, rp, L, w, RT, pl.policy_blocks, s, &nnorm_a)) ||
+        (rc = actor_backward(h, ap, d, rp, L, w, RT, pl.policy_blocks, s, &nnorm_a, h->slab_ffn)) ||
         (rc = ma_gate_apply(h, nnorm_c, nnorm_a, adam_step + k, s)))
       return rc;
     hipLaunchKernelGGL(ppo_stats_kernel, dim3(1), dim3(64), 0, s, (const float*)h->stats,
@@ -81,6 +81,7 @@ int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStr
   pl.epochs = E;
   pl.hoisted = hoisted;
   h->last = pl;
+  h->last_ffn = a2c_actor_report(ap);
   h->last_T = T;
   h->last_R = R;
   return MQ_OK;

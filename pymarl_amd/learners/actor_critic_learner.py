@@ -3,7 +3,8 @@
 
 The critic is a V network (`critic_type`: `cv_critic` on the state, `ac_critic` on the agent's own obs) trained in ONE
 optimiser step over every t against n-step returns of the target critic (`q_nstep`, `add_value_last_step`); the actor
-is the GRU agent with a softmax policy (`agent_output_type: pi_logits`, `action_selector: soft_policies`, no epsilon
+is the GRU agent, or under `use_rnn: False` (what epymarl's maa2c.yaml / ia2c.yaml ship) the feed-forward agent as two
+fused kernels (pymarl_amd/csrc/ffn_actor_kernels.hpp), with a softmax policy (`agent_output_type: pi_logits`, `action_selector: soft_policies`, no epsilon
 floor), trained with the advantage td = (return - V) mask and an entropy bonus (`entropy_coef`). All of train() is one
 launch sequence of hand-written HIP kernels (include/ma_a2c.h, pymarl_amd/csrc/a2c_kernels.hpp); torch only owns the
 buffers. There is no CPU path. One synchronisation per train(): the stats read-back that says whether the batch had a
@@ -13,8 +14,8 @@ Keys: `lr` (both optimisers), `optimizer` (absent or `adam`: torch.optim.Adam wi
 keys.optimizer_config; `rmsprop`: the reference's RMSprop), `grad_norm_clip`, `target_update_interval_or_tau`
 (keys.target_update_config's rules counted in critic training steps; absent: a hard update every
 `target_update_interval`, default 200, critic training steps), `standardise_rewards` (keys.reward_norm_config),
-`hidden_dim` (the critic's width, 64 or 128), `mask_before_softmax` (default True). Refused with ValueError:
-`use_rnn: False`, `learner_dp`, `standardise_returns: True`, `obs_individual_obs: True`, a critic_type other than the
+`hidden_dim` (the critic's width, 64 or 128), `mask_before_softmax` (default True), `use_rnn` (True, False or absent).
+Refused with ValueError: `learner_dp`, `standardise_returns: True`, `obs_individual_obs: True`, a critic_type other than the
 two, and a PrioritizedReplayBuffer batch.
 """
 from __future__ import annotations
@@ -29,7 +30,7 @@ from torch.optim import Adam, RMSprop
 
 from .. import _lib
 from ..components.episode_buffer import is_per_batch, is_replay_view, replay_view
-from ..modules.agents.rnn_agent import obs_dim, use_rnn_config
+from ..modules.agents.rnn_agent import agent_kind, obs_dim, use_rnn_config
 from ..modules.critics import REGISTRY as critic_REGISTRY
 from ..modules.flat import link, load_state, pack, rebind, state_buffers, state_dict_own_steps, to_current_device
 from .keys import (REW_MS_INIT, hard_target_update, load_rew_ms, optimizer_config, reward_norm_config, reward_stats,
@@ -51,9 +52,7 @@ def a2c_config(args):
     ct = getattr(args, "critic_type", None)
     if ct not in CRITIC_TYPES:
         raise ValueError("critic_type {!r} not recognised (one of {}).".format(ct, ", ".join(CRITIC_TYPES)))
-    if not use_rnn_config(args):
-        raise ValueError("ActorCriticLearner does not support use_rnn: False (the feed-forward agent): its actor is "
-                         "the GRU agent.")
+    use_rnn_config(args)   # True, False or absent: anything else is refused there
     if getattr(args, "learner_dp", False):
         raise ValueError("learner_dp is not supported by ActorCriticLearner.")
     if getattr(args, "standardise_returns", False):
@@ -104,6 +103,7 @@ def make_a2c_config(args, ac, input_dim, critic, max_batch, max_seq, gpow):
     cfg.gamma_pow = gpow.ctypes.data
     cfg.max_batch = int(max_batch)
     cfg.max_seq = int(max_seq)
+    cfg.agent = agent_kind(args)   # use_rnn: False selects the feed-forward actor
     return cfg
 
 
@@ -111,6 +111,10 @@ class ActorCriticLearner:
     def __init__(self, mac, scheme, logger, args):
         self.args = args
         self.cfg = a2c_config(args)
+        # the library's actor follows the key, the MAC's module its own construction: they must be the same agent
+        if getattr(mac.agent, "use_rnn", True) != use_rnn_config(args):
+            raise ValueError("use_rnn: {} but the MAC's agent is {}: build the MAC from the same args.".format(
+                use_rnn_config(args), "the GRU agent" if getattr(mac.agent, "use_rnn", True) else "the feed-forward one"))
         self.n_agents = args.n_agents
         self.n_actions = args.n_actions
         self.mac = mac
@@ -273,10 +277,12 @@ class ActorCriticLearner:
         return dict(self._last)
 
     def last_plan(self):
-        """What the last train() launched (ma_last_plan): rows, k / kp, split-K slices, blocks per launch."""
-        pl = _lib.MAPlan()
+        """What the last train() launched (ma_last_plan, ma_last_actor): rows, k / kp, split-K slices, blocks per launch, and with
+        the feed-forward actor its tiles, workgroups and the forward's LDS bytes."""
+        pl, fp = _lib.MAPlan(), _lib.MAActor()
         _lib.check(self._handle.lib.ma_last_plan(self._handle.h, ctypes.byref(pl)))
-        return pl.as_dict()
+        _lib.check(self._handle.lib.ma_last_actor(self._handle.h, ctypes.byref(fp)))
+        return dict(pl.as_dict(), **fp.as_dict())
 
     def last_intermediate(self, which):
         """0: V' (B, T+1, n); 1: V (B, T, n); 2: the n-step returns (B, T, n); 3: pi (B, T, n, A); 4: dLoss/dlogits
