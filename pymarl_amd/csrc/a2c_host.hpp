@@ -1,36 +1,28 @@
-// Host side of the actor-critic learner step (include/ma_a2c.h). As the COMA learner it keeps an
-// internal mq_handle (no mixer) for the agent's workspace and kernels and shares the actor's forward and backward with
-// it (coma_host.hpp actor_forward / actor_backward, launched from a2c_plan's ActorPlan); the critic has its own
-// workspace, sized once at ma_create from max_batch / max_seq.
+// Host side of the actor-critic learner step (include/ma_a2c.h). Its actor is the one the COMA learner
+// has (actor_host.hpp: an internal mq_handle with no mixer for the agent's workspace and kernels, actor_forward /
+// actor_backward launched from a2c_plan's ActorPlan); the critic has its own workspace, sized once at ma_create from
+// max_batch / max_seq.
 #pragma once
 #include <cmath>
 
 #include "../../include/ma_a2c.h"
 #include "a2c_kernels.hpp"
-#include "coma_host.hpp"
-#include "optim_host.hpp"
+#include "actor_host.hpp"
 #include "ppo_kernels.hpp"
 
 struct ma_handle {
   ma_config cfg;
-  mq_handle* ah = nullptr;   // agent workspace + kernels
-  int K, Kp, Hc, Ap;
-  int64_t aoff[MQ_P_COUNT + 1];
+  Actor a;   // the agent's handle, bound buffers and workspace
+  int K, Kp, Hc;
   int64_t coff[MA_P_COUNT + 1];
-  int64_t Pa, Pc;
-  float *agent = nullptr, *agrad = nullptr, *asq = nullptr, *critic = nullptr, *tcritic = nullptr, *cgrad = nullptr,
-        *csq = nullptr, *stats = nullptr;
+  int64_t Pc;
+  float *critic = nullptr, *tcritic = nullptr, *cgrad = nullptr, *csq = nullptr, *stats = nullptr;
   DevBuf<float> ws;     // one allocation, carved by ma_create's table
   DevBuf<float> gpow;   // [q_nstep + 2] float32(gamma ** k)
   // critic workspace
   float *X, *H1t, *H2t, *H1o, *H2o, *Vt, *Vo, *RS, *ret, *td, *dH2, *dH1, *slab_w3, *cpart, *slab_w2, *slab_w1,
       *cred_tmp, *cnorm_part;
   int* halt;
-  // actor workspace
-  float *dL, *dHo, *pi, *ppart, *slab_fc2, *red_tmp, *norm_part;
-  float* slab_ffn;   // [ffn_slabs_max][len_rnn] the feed-forward actor's [dWr | dbr | dW2 | db2] slabs
-  int ffn_slabs_max = 0, ffn_cap = 0;   // slabs slab_ffn holds; MQ_PLAN ffn_actor_blocks (0: the default cap)
-  bool ffn_attr = false;   // the two ffn_actor kernels' dynamic-LDS attributes are raised
   float *old_lp, *ratio;   // [T R] each, PPO: epoch 0's log-probabilities of the taken actions, the last epoch's ratio
   float* gbak;   // [Pa + MQ_NSUMS | Pc + MA_NTAIL] both gradient buffers before the reductions (a2c_gate_kernel)
   double* rbak;  // [3] the running reward statistics before reward_norm_kernel merged the batch into them
@@ -44,7 +36,7 @@ struct ma_handle {
   ma_actor last_ffn{};
   int last_T = 0, last_R = 0;
 
-  ~ma_handle() { mq_destroy(ah); }   // the buffers free themselves
+  ~ma_handle() { mq_destroy(a.ah); }   // the buffers free themselves
 };
 
 namespace {
@@ -162,7 +154,7 @@ int ma_returns(const ma_handle* h, const ADims& cd, const Rep& rp, const ma_plan
   const ma_config& c = h->cfg;
   if (h->rew_state) {
     MQ_HIP(hipMemcpyAsync(h->rbak, h->rew_state, 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    const Dims dr = mq::make_dims(h->ah->cfg, cd.B, cd.Tp, cd.t_stride);   // dr.T = T, dr.M = T B
+    const Dims dr = mq::make_dims(h->a.ah->cfg, cd.B, cd.Tp, cd.t_stride);   // dr.T = T, dr.M = T B
     hipLaunchKernelGGL(reward_norm_kernel, dim3(1), dim3(RN_THREADS), 0, s, dr, rp, h->rew_state, h->RS);
     MQ_HIP(hipGetLastError());
   }
@@ -173,42 +165,34 @@ int ma_returns(const ma_handle* h, const ADims& cd, const Rep& rp, const ma_plan
   return MQ_OK;
 }
 
-// The step's plan and its actor's, checked against what ma_create allocated (max_batch / max_seq bound the slabs, and
-// PPO's old_lp and ratio; the feed-forward actor's slabs) and against the n-step pass's and the feed-forward forward's
-// LDS. The feed-forward kernels' dynamic LDS is past a launch's default: their attributes are raised once per handle.
-int ma_step_plan(ma_handle* h, int B, int Tp, ma_plan* pl, ActorPlan* ap) {
-  *pl = a2c_plan(h->cfg, B, Tp, h->rew_state != nullptr, h->adam, ap, h->ffn_cap);
-  if (pl->ns_cw1 > h->ns_max || pl->ns_cw2 > h->ns_max || pl->dv_blocks > h->ndv_max || ap->ns_w2 > kNsplitMax ||
-      ap->ffn_blocks > h->ffn_slabs_max)
-    return set_err(MQ_ERR_STATE, "actor-critic plan exceeds the workspace");
-  if (ap->agent == MQ_AGENT_FFN) {
-    if (ap->ffn_fwd_lds > kFfnActorLdsMax) return set_err(MQ_ERR_ARG, "the feed-forward actor's forward exceeds the LDS");
-    MQ_LDS(ffn_actor_fwd_kernel, ap->ffn_fwd_lds);
-    MQ_LDS(ffn_actor_bwd_kernel, kFfnActorBwdLds);
-    if (!h->ffn_attr) {
-      MQ_HIP(hipFuncSetAttribute((const void*)ffn_actor_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)kFfnActorLdsMax));
-      MQ_HIP(hipFuncSetAttribute((const void*)ffn_actor_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)kFfnActorLdsMax));
-      h->ffn_attr = true;
-    }
-  }
+// The step's plan and its actor's step, checked against what ma_create allocated (max_batch / max_seq bound the slabs,
+// and PPO's old_lp and ratio; the feed-forward actor's slabs) and against the n-step pass's and the actor's LDS.
+int ma_step_plan(ma_handle* h, const mq_replay* batch, const Rep& rp, ma_plan* pl, ActorStep* act) {
+  const int B = batch->batch_size, Tp = batch->t_len;
+  ActorPlan ap;
+  *pl = a2c_plan(h->cfg, B, Tp, h->rew_state != nullptr, h->adam, &ap, h->a.ffn_cap);
+  const char* exceeds = "actor-critic plan exceeds the workspace";
+  if (pl->ns_cw1 > h->ns_max || pl->ns_cw2 > h->ns_max || pl->dv_blocks > h->ndv_max)
+    return set_err(MQ_ERR_STATE, exceeds);
+  if (const int rc = actor_prepare(h->a, ap, exceeds)) return rc;
   if (a2c_nstep_lds_bytes(Tp, h->cfg.n_agents) > kA2cNstepLdsMax)
     return set_err(MQ_ERR_ARG, "episode too long for the LDS n-step return pass");
+  *act = make_actor_step(h->a, ap, rp, B, Tp - 1, batch->t_stride);   // the actor unrolls t < T only
   return MQ_OK;
 }
 
 // Both applies after both backwards; an empty batch (M = 0) halts both (a2c_gate_kernel).
 int ma_gate_apply(const ma_handle* h, int nnorm_c, int nnorm_a, int64_t adam_step, hipStream_t s) {
-  const int64_t na = h->Pa + MQ_NSUMS, nc = h->Pc + MA_NTAIL;
+  const Actor& a = h->a;
+  const int64_t na = a.Pa + MQ_NSUMS, nc = h->Pc + MA_NTAIL;
   hipLaunchKernelGGL(a2c_gate_kernel, dim3(1), dim3(A2C_GATE_THREADS), 0, s, (const float*)(h->cgrad + h->Pc), h->halt,
-                     h->stats, (const float*)h->gbak, h->agrad, na, h->cgrad, nc, h->rew_state,
+                     h->stats, (const float*)h->gbak, a.agrad, na, h->cgrad, nc, h->rew_state,
                      (const double*)h->rbak);
   MQ_HIP(hipGetLastError());
   int rc;
   if ((rc = ma_apply(h, h->critic, h->cgrad, h->adam ? h->ad.critic_exp_avg : nullptr, h->csq, h->Pc, h->cnorm_part,
                      nnorm_c, adam_step, h->stats, s)) ||
-      (rc = ma_apply(h, h->agent, h->agrad, h->adam ? h->ad.agent_exp_avg : nullptr, h->asq, h->Pa, h->norm_part,
+      (rc = ma_apply(h, a.agent, a.agrad, h->adam ? h->ad.agent_exp_avg : nullptr, a.asq, a.Pa, a.norm_part,
                      nnorm_a, adam_step, h->stats + 8, s)))
     return rc;
   return MQ_OK;
@@ -268,35 +252,26 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
   int rc = ma_check_config(c, true);
   if (rc) return rc;
   if (c.max_batch * c.n_agents > MQ_INLINE_IDS * 64) return set_err(MQ_ERR_ARG, "max_batch * n_agents too large");
+  std::unique_ptr<ma_handle> h(new ma_handle());   // a failure below frees it and the agent handle it owns
   const mq_config ac = agent_config(c, c.gamma_pow[1], c.agent);   // (ma_check_config: gamma_pow is not NULL)
-  mq_handle* ah = nullptr;
-  if ((rc = mq_create(&ac, &ah))) return rc;
-  std::unique_ptr<ma_handle> h(new ma_handle());   // owns ah from here: a failure below frees both
+  if ((rc = mq_create(&ac, &h->a.ah))) return rc;
   h->cfg = c;
   h->cfg.gamma_pow = nullptr;   // the caller's table is copied below and not kept
-  h->ah = ah;
-  for (int i = 0; i <= MQ_P_COUNT; ++i) h->aoff[i] = ah->off[i];
-  h->Pa = ah->P;
-  const int n = c.n_agents, A = c.n_actions, Hc = c.critic_hidden;
+  const int n = c.n_agents, Hc = c.critic_hidden;
   h->K = a2c_k(c);
   h->Kp = (h->K + 3) & ~3;
   h->Hc = Hc;
-  h->Ap = (A + 3) & ~3;
   ma_offsets(c, h->coff);
   h->Pc = h->coff[MA_P_COUNT];
 
   const int64_t Tp = c.max_seq, R = (int64_t)c.max_batch * n, T = Tp - 1, RT = T * R;
   h->ns_max = a2c_ns_max(RT);
   h->ndv_max = (int)((RT + A2C_DV_ROWS - 1) / A2C_DV_ROWS);
-  const bool ffn = c.agent == MQ_AGENT_FFN;
-  h->ffn_slabs_max = ffn ? ffn_actor_blocks_max(RT) : 0;
-  h->ffn_cap = plan_int("ffn_actor_blocks", 0);   // the one read of this MQ_PLAN item per handle
+  h->a.ffn_cap = plan_int("ffn_actor_blocks", 0);   // the one read of this MQ_PLAN item per handle
   const int64_t lw1 = (int64_t)Hc * h->K + Hc, lw2 = (int64_t)Hc * Hc + Hc, lw3 = Hc + 1;
   const int64_t cred_tmp = kRedZ * (lw1 + lw2 + lw3 + 8);
-  const int64_t red_tmp = kRedZ * ((int64_t)mq::H * ah->I + mq::H) + kRedZ * ah->len_rnn + kRedZ * (A * mq::H + A) +
-                          kRedZ * 8;
   float* rbak_f = nullptr;
-  const WsTable ws = {
+  WsTable ws = {
       {"X", Tp * R * h->Kp, &h->X},
       {"H1t", Tp * R * Hc, &h->H1t}, {"H2t", Tp * R * Hc, &h->H2t},
       {"H1o", RT * Hc, &h->H1o}, {"H2o", RT * Hc, &h->H2o},
@@ -308,16 +283,14 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
       {"slab_w2", h->ns_max * lw2, &h->slab_w2}, {"slab_w1", h->ns_max * lw1, &h->slab_w1},
       {"cred_tmp", cred_tmp, &h->cred_tmp}, {"cnorm_part", kNormPartMax, &h->cnorm_part},
       {"halt", 8, nullptr, &h->halt},
-      {"dL", RT * h->Ap, &h->dL}, {"dHo", RT * mq::H, &h->dHo}, {"pi", RT * A, &h->pi},
-      {"ppart", ((RT + 3) / 4) * 8, &h->ppart},
-      {"slab_fc2", (int64_t)kNsplitMax * (A * mq::H + A), &h->slab_fc2},
-      {"slab_ffn", h->ffn_slabs_max * ah->len_rnn, &h->slab_ffn},
-      {"red_tmp", red_tmp, &h->red_tmp},
-      {"norm_part", kNormPartMax, &h->norm_part},
-      {"old_lp", RT, &h->old_lp}, {"ratio", RT, &h->ratio},
-      {"gbak", h->Pa + MQ_NSUMS + h->Pc + MA_NTAIL, &h->gbak},
-      {"rbak", 8, &rbak_f},   // three doubles (every row starts at a multiple of 64 floats: 8-byte aligned)
   };
+  const WsTable actor_rows = actor_ws_rows(h->a, c.n_actions, *h->a.ah, RT);
+  ws.insert(ws.end(), actor_rows.begin(), actor_rows.end());
+  ws.insert(ws.end(), {
+      {"old_lp", RT, &h->old_lp}, {"ratio", RT, &h->ratio},
+      {"gbak", h->a.Pa + MQ_NSUMS + h->Pc + MA_NTAIL, &h->gbak},
+      {"rbak", 8, &rbak_f},   // three doubles (every row starts at a multiple of 64 floats: 8-byte aligned)
+  });
   if ((rc = ws_carve(h->ws, ws, "actor-critic workspace hipMalloc"))) return rc;
   h->rbak = (double*)rbak_f;
   const int64_t ng = (int64_t)c.q_nstep + 2;
@@ -334,8 +307,7 @@ int ma_destroy(ma_handle* h) {
 
 int ma_param_offsets(const ma_handle* h, int64_t* agent_offsets, int64_t* critic_offsets) {
   if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
-  if (agent_offsets)
-    for (int i = 0; i <= MQ_P_COUNT; ++i) agent_offsets[i] = h->aoff[i];
+  if (agent_offsets) (void)mq_param_offsets(h->a.ah, agent_offsets);
   if (critic_offsets)
     for (int i = 0; i <= MA_P_COUNT; ++i) critic_offsets[i] = h->coff[i];
   return MQ_OK;
@@ -345,10 +317,8 @@ int ma_bind(ma_handle* h, float* agent, float* agent_grad, float* agent_sq, floa
             float* critic_grad, float* critic_sq, float* stats) {
   if (!h || !agent || !agent_grad || !agent_sq || !critic || !target_critic || !critic_grad || !critic_sq || !stats)
     return set_err(MQ_ERR_ARG, "ma_bind: NULL pointer");
-  h->agent = agent; h->agrad = agent_grad; h->asq = agent_sq; h->critic = critic; h->tcritic = target_critic;
-  h->cgrad = critic_grad; h->csq = critic_sq; h->stats = stats;
-  // the agent handle: online = target = the agent params (the actor has no target net); its stats land at stats + 8
-  return mq_bind(h->ah, agent, agent, agent_grad, agent_sq, stats + 8, nullptr);
+  h->critic = critic; h->tcritic = target_critic; h->cgrad = critic_grad; h->csq = critic_sq; h->stats = stats;
+  return actor_bind(h->a, agent, agent_grad, agent_sq, stats);
 }
 
 int ma_set_adam(ma_handle* h, const ma_adam* a) {
@@ -376,9 +346,9 @@ int ma_set_reward_norm(ma_handle* h, double* state) {
 }
 
 int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void* stream) {
-  if (!h || !h->agent) return set_err(MQ_ERR_STATE, "ma_train_step before ma_bind");
-  mq_handle* ah = h->ah;
-  int rc = check_batch(ah, batch);
+  if (!h || !h->a.agent) return set_err(MQ_ERR_STATE, "ma_train_step before ma_bind");
+  const Actor& a = h->a;
+  int rc = check_batch(a.ah, batch);
   if (rc || (rc = ma_check_replay(h->cfg, batch, "ma_train_step"))) return rc;
   if (h->adam && adam_step < 1) return set_err(MQ_ERR_ARG, "ma_train_step: adam_step is the 1-based step number (>= 1)");
   hipStream_t s = (hipStream_t)stream;
@@ -389,8 +359,8 @@ int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void*
   const Rep rp = make_rep(batch);
   const ADims cd = ma_dims(c, B, Tp, batch->t_stride);
   ma_plan pl;
-  ActorPlan ap;
-  if ((rc = ma_step_plan(h, B, Tp, &pl, &ap))) return rc;
+  ActorStep act;
+  if ((rc = ma_step_plan(h, batch, rp, &pl, &act))) return rc;
   pl.epochs = 1;
   const int64_t RT = (int64_t)T * R, RTp = (int64_t)Tp * R;
 
@@ -418,37 +388,32 @@ int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void*
                      (const float*)h->H2o, tc, oc, h->coff[MA_P_FC3_W], h->coff[MA_P_FC3_B], Hc, RTp, RT, h->Vt, h->Vo, R,
                      n, 0);
   MQ_HIP(hipGetLastError());
-  // ---- the agent's dims: the actor unrolls t < T only
-  const Dims d = mq::make_dims(ah->cfg, B, T, batch->t_stride);   // d.Tp = T: d.RT() = T R
   if ((rc = ma_returns(h, cd, rp, pl, s))) return rc;
   hipLaunchKernelGGL(a2c_dv_kernel, dim3(pl.dv_blocks), dim3(256), 0, s, cd, rp, (const float*)h->ret,
                      (const float*)h->Vo, (const float*)h->H2o, oc + h->coff[MA_P_FC3_W], h->td, h->dH2, h->slab_w3,
                      h->cpart);
   MQ_HIP(hipGetLastError());
   // ---- actor forward and policy (reads the critic's td as the advantage)
-  const Lay L = make_lay(ah);
-  Work w = ah->w;
-  w.dHo = h->dHo;
-  if ((rc = actor_forward(h, ap, d, rp, L, w, RT, s))) return rc;
-  hipLaunchKernelGGL(a2c_policy_kernel, dim3(pl.policy_blocks), dim3(256), 0, s, d, rp, (const float*)w.Q,
-                     (const float*)h->td, c.entropy_coef, (int)(c.mask_before_softmax != 0), h->Ap, h->dL, h->pi,
-                     h->ppart);
+  if ((rc = actor_forward(a, act, s))) return rc;
+  hipLaunchKernelGGL(a2c_policy_kernel, dim3(pl.policy_blocks), dim3(256), 0, s, act.d, rp, (const float*)act.w.Q,
+                     (const float*)h->td, c.entropy_coef, (int)(c.mask_before_softmax != 0), a.Ap, a.dL, a.pi,
+                     a.ppart);
   MQ_HIP(hipGetLastError());
   // ---- critic backward: dH1, the split-K weight gradients, the two-pass reduction into cgrad [Pc | MA_NTAIL]
   if ((rc = ma_critic_dw(h, pl, RT, s))) return rc;
   // both gradient buffers as the caller left them: an empty batch puts them back (a2c_gate_kernel)
-  const int64_t na = h->Pa + MQ_NSUMS, nc = h->Pc + MA_NTAIL;
-  MQ_HIP(hipMemcpyAsync(h->gbak, h->agrad, (size_t)na * sizeof(float), hipMemcpyDeviceToDevice, s));
+  const int64_t na = a.Pa + MQ_NSUMS, nc = h->Pc + MA_NTAIL;
+  MQ_HIP(hipMemcpyAsync(h->gbak, a.agrad, (size_t)na * sizeof(float), hipMemcpyDeviceToDevice, s));
   MQ_HIP(hipMemcpyAsync(h->gbak + na, h->cgrad, (size_t)nc * sizeof(float), hipMemcpyDeviceToDevice, s));
   int nnorm_c;
   if ((rc = ma_critic_reduce(h, pl, s, &nnorm_c))) return rc;
   // ---- actor backward (the COMA learner's chain)
   int nnorm_a;
-  if ((rc = actor_backward(h, ap, d, rp, L, w, RT, pl.policy_blocks, s, &nnorm_a, h->slab_ffn))) return rc;
+  if ((rc = actor_backward(a, act, pl.policy_blocks, s, &nnorm_a))) return rc;
   // ---- both applies after both backwards; an empty batch (M = 0) halts both
   if ((rc = ma_gate_apply(h, nnorm_c, nnorm_a, adam_step, s))) return rc;
   h->last = pl;
-  h->last_ffn = a2c_actor_report(ap);
+  h->last_ffn = a2c_actor_report(act.ap);
   h->last_T = T;
   h->last_R = R;
   return MQ_OK;
@@ -477,8 +442,8 @@ int ma_copy_intermediate(ma_handle* h, int which, float* dst, int64_t* count, vo
     case 0: src = h->Vt; cnt = TR + h->last_R; break;
     case 1: src = h->Vo; cnt = TR; break;
     case 2: src = h->ret; cnt = TR; break;
-    case 3: src = h->pi; cnt = TR * h->cfg.n_actions; break;
-    case 4: src = h->dL; cnt = TR * h->Ap; break;
+    case 3: src = h->a.pi; cnt = TR * h->cfg.n_actions; break;
+    case 4: src = h->a.dL; cnt = TR * h->a.Ap; break;
     case 5: case 6:
       if (h->last.hoisted < 1) return set_err(MQ_ERR_STATE, "the last train step was not a PPO step");
       src = which == 5 ? h->old_lp : h->ratio; cnt = TR; break;

@@ -1,11 +1,23 @@
-// What the policy-gradient actor of the COMA, actor-critic and PPO learners launches (coma_host.hpp actor_forward /
-// actor_backward), decided from the shape without a HIP call. coma_plan and a2c_plan both take their actor items from
-// here, so what a plan reports is what the launches read.
+// The policy-gradient actor of the COMA, actor-critic and PPO learners without a HIP call: what a handle holds of it
+// (Actor), its workspace rows (actor_ws_rows, probe: tests/host/actor_ws_probe.cpp), what a step launches (ActorPlan:
+// coma_plan and a2c_plan report it, actor_host.hpp launches from it) and its backward's reduction (actor_reduce_plan).
 #pragma once
 #include "ffn_actor_kernels.hpp"
-#include "step_plan.hpp"
+#include "reduce_plan.hpp"
 
 namespace mq {
+
+// A learner handle's actor. The agent's own buffers (X1 .. slab_fc1, slab_rnn) are the agent handle's workspace.
+struct Actor {
+  mq_handle* ah = nullptr;   // the agent's handle (no mixer): layout, workspace, kernels; owned by the learner's handle
+  float *agent = nullptr, *agrad = nullptr, *asq = nullptr;   // bound: parameters, gradient [Pa | MQ_NSUMS], square_avg
+  int64_t Pa = 0;      // the agent's parameters
+  int Ap = 0;          // dL's pitch: the actions rounded up to 4
+  // workspace (actor_ws_rows); slab_ffn [ffn_slabs_max][len_rnn]: the feed-forward actor's slabs
+  float *dL, *dHo, *pi, *ppart, *slab_fc2, *slab_ffn, *red_tmp, *norm_part;
+  int ffn_slabs_max = 0, ffn_cap = 0;   // slabs slab_ffn holds; MQ_PLAN ffn_actor_blocks (0: the default cap)
+  bool ffn_attr = false;   // the two ffn_actor kernels' dynamic-LDS attributes are raised
+};
 
 struct ActorPlan {
   bool fused_fwd;   // gru_fwd_fused_kernel; else fc1 / gi GEMMs, gru_fwd<rw_fwd>, fc2 GEMM
@@ -23,7 +35,7 @@ struct ActorPlan {
   size_t ffn_fwd_lds;   // the forward's dynamic LDS, bytes
 };
 
-// Most workgroups (slabs) ffn_actor_bwd_kernel runs over any step with at most RTmax rows: what ma_create allocates.
+// Most workgroups (slabs) ffn_actor_bwd_kernel runs over any step with at most RTmax rows: what slab_ffn holds.
 inline int ffn_actor_blocks_max(int64_t RTmax) {
   return (int)std::min<int64_t>(kFfnActorBlocks, std::max<int64_t>(1, (RTmax + FA_ROWS - 1) / FA_ROWS));
 }
@@ -50,6 +62,57 @@ inline ActorPlan actor_plan(int I, int O, int A, int n, int R, int64_t RT, int a
   p.nblk_bwd = (R + p.rw_bwd - 1) / p.rw_bwd;
   p.ns_w2 = split_k_slices(RT, 1);
   return p;
+}
+
+// The internal agent handle's config (no mixer) from a COMA or an actor-critic config `c`; `agent`: MQ_AGENT_*.
+template <class C>
+mq_config agent_config(const C& c, float gamma, int agent = MQ_AGENT_GRU) {
+  mq_config a{};
+  a.n_agents = c.n_agents; a.n_actions = c.n_actions; a.obs_dim = c.obs_dim; a.state_dim = c.state_dim;
+  a.rnn_hidden_dim = c.rnn_hidden_dim; a.mixer = MQ_MIXER_NONE;
+  a.obs_last_action = c.obs_last_action; a.obs_agent_id = c.obs_agent_id; a.gamma = gamma; a.lr = c.lr;
+  a.optim_alpha = c.optim_alpha; a.optim_eps = c.optim_eps; a.grad_norm_clip = c.grad_norm_clip;
+  a.max_batch = c.max_batch; a.max_seq = c.max_seq;
+  a.agent = agent;
+  return a;
+}
+
+// The actor's rows of a learner's workspace table, for the agent layout y and steps of at most RTmax = T R rows; the
+// capacities they give land in `a` with the pointers.
+inline WsTable actor_ws_rows(Actor& a, int A, const Layout& y, int64_t RTmax) {
+  const int64_t l1 = (int64_t)H * y.I + H, l2 = (int64_t)A * H + A;
+  a.Pa = y.P;
+  a.Ap = (A + 3) & ~3;
+  a.ffn_slabs_max = y.ffn ? ffn_actor_blocks_max(RTmax) : 0;
+  // pass 1's partials: at most kRedZ groups of each region's length (RedBuilder::add). GRU: [dW1 | db1], the BPTT
+  // slabs' W_ih .. b_hh prefix (shorter than len_rnn), [dW2 | db2], the loss sums. Feed-forward: [dW1 | db1], the whole
+  // len_rnn of a [dWr | dbr | dW2 | db2] slab, the loss sums, and no region of fc2's own: the one sum covers both
+  const int64_t red_tmp = kRedZ * (l1 + y.len_rnn + l2 + MQ_NSUMS);
+  return {
+      {"dL", RTmax * a.Ap, &a.dL}, {"dHo", RTmax * H, &a.dHo}, {"pi", RTmax * A, &a.pi},
+      {"ppart", ((RTmax + 3) / 4) * MQ_NSUMS, &a.ppart},
+      {"slab_fc2", kNsplitMax * l2, &a.slab_fc2},
+      {"slab_ffn", a.ffn_slabs_max * y.len_rnn, &a.slab_ffn},
+      {"red_tmp", red_tmp, &a.red_tmp},
+      {"norm_part", kNormPartMax, &a.norm_part},
+  };
+}
+
+// The regions of the actor's backward into a.agrad [Pa | MQ_NSUMS], from the policy kernel's npol blocks of loss sums
+// and the slabs the plan's launches leave in `w` (the agent handle's workspace) and `a`. No launch, as plan_reduce.
+inline RedBuilder actor_reduce_plan(const ActorPlan& p, const Layout& y, const Work& w, const Actor& a, int npol) {
+  RedBuilder rb(a.red_tmp);
+  rb.add(w.slab_fc1, p.ns_w1, (int64_t)H * y.I + H, a.agrad + y.off[MQ_P_FC1_W], true);
+  if (p.agent == MQ_AGENT_FFN) {   // one slab per workgroup of ffn_actor_bwd_kernel
+    rb.add(a.slab_ffn, p.ffn_blocks, y.len_rnn, a.agrad + y.off[MQ_P_FFN_W], true);
+  } else {
+    // W_ih .. b_hh: the prefix of each BPTT slab; its fc2 part (unused in the dense-dy mode) is as long as fc2's slab
+    const int64_t pre = y.off[MQ_P_FC2_W] - y.off[MQ_P_RNN_W_IH];
+    rb.add(w.slab_rnn, p.nblk_bwd, pre, a.agrad + y.off[MQ_P_RNN_W_IH], true, y.len_rnn);
+    rb.add(a.slab_fc2, p.ns_w2, y.len_rnn - pre, a.agrad + y.off[MQ_P_FC2_W], true);
+  }
+  rb.add(a.ppart, npol, MQ_NSUMS, a.agrad + a.Pa, false);
+  return rb;
 }
 
 }  // namespace mq

@@ -1,24 +1,18 @@
 // Host side of the COMA learner step (include/mc_coma.h). It shares the QMIX learner's error handling
-// (host_util.hpp), replay plumbing (learner_handle.hpp) and agent kernels. The agent (RNNAgent) forward / BPTT reuses
-// an internal mq_handle (no mixer) for its workspace; the critic has its own. What a step launches is coma_plan's
-// answer (coma_plan.hpp), fixed before the first launch; ComaStep launches it phase by phase and decides nothing.
+// (host_util.hpp), replay plumbing (learner_handle.hpp) and agent kernels. The actor is actor_host.hpp's (the agent's
+// forward / BPTT on an internal mq_handle with no mixer); the critic has its own workspace. What a step launches is
+// coma_plan's answer (coma_plan.hpp), fixed before the first launch; ComaStep launches it phase by phase.
 #pragma once
 #include "../../include/mc_coma.h"
+#include "actor_host.hpp"
 #include "coma_plan.hpp"
-#include "gru_fwd_fused.hpp"
-#include "gru_kernels.hpp"
-#include "learner_handle.hpp"
-#include "optim_host.hpp"
 
 struct mc_handle {
   mc_config cfg;
-  mq_handle* ah = nullptr;   // agent workspace + kernels
-  int I, Kc, Kp, Ap;
-  int64_t aoff[MQ_P_COUNT + 1];
+  Actor a;   // the agent's handle, bound buffers and workspace
   int64_t coff[MC_P_COUNT + 1];
-  int64_t Pa, Pc;
-  float *agent = nullptr, *agrad = nullptr, *asq = nullptr, *critic = nullptr, *tcritic = nullptr,
-        *cgrad = nullptr, *csq = nullptr, *stats = nullptr;
+  int64_t Pc;
+  float *critic = nullptr, *tcritic = nullptr, *cgrad = nullptr, *csq = nullptr, *stats = nullptr;
   DevBuf<float> ws;   // one allocation, carved by mc_create's table
   // critic workspace
   float *X, *H1t, *H2t, *Qt, *tgt, *msum, *H1p, *H1c, *H2c, *dH1c, *dH2c, *dqc, *qvals, *cpart, *cnorm, *crec;
@@ -26,8 +20,6 @@ struct mc_handle {
   float* Pbak;   // [2][Pc] critic params / square_avg before the chain: restored if a hand-off times out
   int* actc;
   int* cstate;
-  // actor workspace
-  float *dL, *dHo, *pi, *ppart, *slab_fc2, *red_tmp, *norm_part;
   int last_T = 0, last_R = 0, last_Rc = 0;
   bool timing = false;
   // persistent critic chain (coma_chain.hpp): off with MQ_PLAN coma_chain=0, or where cc_ok rejects the shape
@@ -55,7 +47,7 @@ struct mc_handle {
     if (comm && comm_owned) (void)ncclCommDestroy(comm);
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
-    mq_destroy(ah);
+    mq_destroy(a.ah);
   }
 };
 
@@ -95,115 +87,6 @@ mq_replay shard_replay(const mc_config& c, const mq_replay& b, int lo, int hi) {
     s.n_episodes = b.n_episodes - lo;
   }
   return s;
-}
-
-// The internal agent handle's config (no mixer) from a COMA or an actor-critic config `c`; `agent`: MQ_AGENT_*.
-template <class C>
-mq_config agent_config(const C& c, float gamma, int agent = MQ_AGENT_GRU) {
-  mq_config a{};
-  a.n_agents = c.n_agents; a.n_actions = c.n_actions; a.obs_dim = c.obs_dim; a.state_dim = c.state_dim;
-  a.rnn_hidden_dim = c.rnn_hidden_dim; a.mixer = MQ_MIXER_NONE;
-  a.obs_last_action = c.obs_last_action; a.obs_agent_id = c.obs_agent_id; a.gamma = gamma; a.lr = c.lr;
-  a.optim_alpha = c.optim_alpha; a.optim_eps = c.optim_eps; a.grad_norm_clip = c.grad_norm_clip;
-  a.max_batch = c.max_batch; a.max_seq = c.max_seq;
-  a.agent = agent;
-  return a;
-}
-
-// The policy-gradient actor of the COMA and the actor-critic learners (a2c_host.hpp). `h` is either learner's handle:
-// its agent handle h->ah lends the workspace `w` (w.dHo the learner's), h->agent are the agent's parameters, RT = T R
-// the actor's rows. Which kernels and how many slices is ActorPlan's answer (actor_plan.hpp).
-//
-// The agent unroll over t < T, online net only: the logits land in w.Q. The feed-forward actor is one launch
-// (ffn_actor_fwd_kernel: X1, Hh = w.Hs, the logits and XIN).
-template <class Hd>
-int actor_forward(const Hd* h, const ActorPlan& ap, const Dims& d, const Rep& rpa, const Lay& L, const Work& w,
-                  int64_t RT, hipStream_t st) {
-  const mq_handle* ah = h->ah;
-  const float* Pa = h->agent;
-  if (ap.agent == MQ_AGENT_FFN) {
-    const FfnActorFwd p{d, rpa, Pa, ah->off[MQ_P_FC1_W], ah->off[MQ_P_FC1_B], ah->off[MQ_P_FFN_W], ah->off[MQ_P_FFN_B],
-                        ah->off[MQ_P_FC2_W], ah->off[MQ_P_FC2_B], w.X1, w.Hs, w.Q, w.XIN, RT, ap.ffn_tiles,
-                        ap.ffn_resident};
-    hipLaunchKernelGGL(ffn_actor_fwd_kernel, dim3(ap.ffn_fwd_blocks), dim3(256), ap.ffn_fwd_lds, st, p);
-    MQ_HIP(hipGetLastError());
-    return MQ_OK;
-  }
-  if (ap.fused_fwd) {
-    launch_fwd_fused(dim3(d.R, 1), st, d, rpa, Pa, Pa, L, w);
-    MQ_HIP(hipGetLastError());
-    return MQ_OK;
-  }
-  Fc1Prob p1{d, rpa, Pa, Pa, ah->off[MQ_P_FC1_W], ah->off[MQ_P_FC1_B], w.X1, w.XIN, RT};
-  MQ_HIP(launch_gemm(p1, (int)RT, 2 * mq::H, 1, st));
-  GiProb p2{w.X1, Pa, Pa, ah->off[MQ_P_RNN_W_IH], ah->off[MQ_P_RNN_B_IH], w.GI, RT};
-  MQ_HIP(launch_gemm(p2, (int)RT, mq::G3, 1, st));
-  const dim3 grid((d.R + ap.rw_fwd - 1) / ap.rw_fwd, 1);
-  if (ap.rw_fwd == 1) hipLaunchKernelGGL((gru_fwd_kernel<1, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-  else if (ap.rw_fwd == 2) hipLaunchKernelGGL((gru_fwd_kernel<2, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-  else if (ap.rw_fwd == 4) hipLaunchKernelGGL((gru_fwd_kernel<4, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-  else hipLaunchKernelGGL((gru_fwd_kernel<8, 0>), grid, dim3(256), 0, st, d, Pa, Pa, L, w);
-  MQ_HIP(hipGetLastError());
-  Fc2Prob p3{w.Hs, Pa, Pa, ah->off[MQ_P_FC2_W], ah->off[MQ_P_FC2_B], w.Q, RT, d.A};
-  MQ_HIP(launch_gemm(p3, (int)RT, d.A, 1, st));
-  return MQ_OK;
-}
-
-// From the policy kernel's h->dL [RT][Ap] (dense dLoss/dlogits) and its npol blocks of loss sums h->ppart: BPTT with
-// the dense output gradient, the split-K weight gradients, and the two-pass reduction into h->agrad [Pa | MQ_NSUMS];
-// *nnorm = the norm partials it left in h->norm_part. The feed-forward actor: ffn_actor_bwd_kernel (dP1 and one
-// [dWr | dbr | dW2 | db2] slab per workgroup into ffn_slab, the learner's), the split-K [dW1 | db1], the reduction.
-template <class Hd>
-int actor_backward(const Hd* h, const ActorPlan& ap, const Dims& d, const Rep& rpa, const Lay& L, const Work& w,
-                   int64_t RT, int npol, hipStream_t s, int* nnorm, float* ffn_slab = nullptr) {
-  const mq_handle* ah = h->ah;
-  const float* Pa = h->agent;
-  const int A = d.A;
-  if (ap.agent == MQ_AGENT_FFN) {
-    const FfnActorBwd p{h->dL, h->Ap, A, Pa + ah->off[MQ_P_FC2_W], Pa + ah->off[MQ_P_FFN_W], w.Hs, w.X1, w.dP1,
-                        ffn_slab, ah->len_rnn, RT, ap.ffn_tiles, ap.ffn_tpb};
-    hipLaunchKernelGGL(ffn_actor_bwd_kernel, dim3(ap.ffn_blocks), dim3(256), kFfnActorBwdLds, s, p);
-    MQ_HIP(hipGetLastError());
-    Dw1Prob p1{d.I, w.dP1, w.XIN, w.slab_fc1, RT, ap.ns_w1};
-    MQ_HIP(launch_gemm(p1, mq::H, d.I, ap.ns_w1, s));
-    RedBuilder rb(h->red_tmp);
-    rb.add(w.slab_fc1, ap.ns_w1, (int64_t)mq::H * d.I + mq::H, h->agrad + ah->off[MQ_P_FC1_W], true);
-    rb.add(ffn_slab, ap.ffn_blocks, ah->len_rnn, h->agrad + ah->off[MQ_P_FFN_W], true);
-    rb.add(h->ppart, npol, MQ_NSUMS, h->agrad + h->Pa, false);
-    return launch_reduce(rb, h->norm_part, "agent", s, nnorm);
-  }
-  {
-    DhoProb p{h->dL, h->Ap, A, Pa + ah->off[MQ_P_FC2_W], w.dHo, RT};
-    MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));
-  }
-  const size_t dyn = ((size_t)2 * d.A * mq::H + d.A) * sizeof(float);
-  if (ap.rw_bwd == 1)
-    hipLaunchKernelGGL((gru_bwd_kernel<1, 0, true>), dim3(ap.nblk_bwd), dim3(512), dyn, s, d, rpa, Pa, L, w,
-                       ah->len_rnn);
-  else
-    hipLaunchKernelGGL((gru_bwd_kernel<2, 0, true>), dim3(ap.nblk_bwd), dim3(512), dyn, s, d, rpa, Pa, L, w,
-                       ah->len_rnn);
-  MQ_HIP(hipGetLastError());
-  {
-    Dx1Prob p{w.dGI, Pa + ah->off[MQ_P_RNN_W_IH], w.X1, w.dP1, RT};
-    MQ_HIP(launch_gemm(p, (int)RT, mq::H, 1, s));
-  }
-  {
-    Dw1Prob p{d.I, w.dP1, w.XIN, w.slab_fc1, RT, ap.ns_w1};
-    MQ_HIP(launch_gemm(p, mq::H, d.I, ap.ns_w1, s));
-  }
-  {
-    Dw2Prob p{h->dL, h->Ap, A, w.Hs, h->slab_fc2, RT, ap.ns_w2};
-    MQ_HIP(launch_gemm(p, A, mq::H, ap.ns_w2, s));
-  }
-  RedBuilder rb(h->red_tmp);
-  rb.add(w.slab_fc1, ap.ns_w1, (int64_t)mq::H * d.I + mq::H, h->agrad + ah->off[MQ_P_FC1_W], true);
-  // W_ih .. b_hh: the prefix of each BPTT slab (its fc2 part is unused in the dense-dy mode)
-  rb.add(w.slab_rnn, ap.nblk_bwd, ah->off[MQ_P_FC2_W] - ah->off[MQ_P_RNN_W_IH], h->agrad + ah->off[MQ_P_RNN_W_IH],
-         true, ah->len_rnn);
-  rb.add(h->slab_fc2, ap.ns_w2, (int64_t)A * mq::H + A, h->agrad + ah->off[MQ_P_FC2_W], true);
-  rb.add(h->ppart, npol, MQ_NSUMS, h->agrad + h->Pa, false);
-  return launch_reduce(rb, h->norm_part, "agent", s, nnorm);
 }
 
 // The critic's three GEMMs over M rows of X [M][Kp] with parameters P at offsets `off` (mc_offsets): H1, H2, then
@@ -277,11 +160,8 @@ struct ComaStep {
   const ComaPlan pl;
   const ComaMode m;
   const CDims cd;
-  const Rep rp;    // the critic's batch: the whole one
-  const Rep rpa;   // the actor's: this rank's episodes under a replicated critic
-  const Dims d;    // the actor's dims (t < T)
-  const Lay L;
-  const Work w;
+  const Rep rp;         // the critic's batch: the whole one
+  const ActorStep act;  // the actor's: this rank's episodes under a replicated critic, t < T
   const float epsilon;
   hipStream_t s;
   bool chained = false;      // the chain's launch was accepted: critic_steps() has nothing to launch
@@ -300,14 +180,11 @@ ComaStep make_coma_step(mc_handle* h, const mq_replay* batch, const ComaPlan& pl
                         hipStream_t s) {
   const mc_config& c = h->cfg;
   // replicated critic: the actor trains this rank's episodes only (the critic sees the whole batch)
-  mq_replay av = m.replicated ? shard_replay(c, *batch, m.shard_lo, m.shard_hi) : *batch;
-  av.t_len = pl.T;
+  const mq_replay av = m.replicated ? shard_replay(c, *batch, m.shard_lo, m.shard_hi) : *batch;
   const Rep rp = make_rep(batch);
-  Work w = h->ah->w;
-  w.dHo = h->dHo;
   return ComaStep{h, pl, m, coma_dims(c, batch->batch_size, batch->t_len, batch->t_stride), rp,
-                  m.replicated ? make_rep(&av) : rp, mq::make_dims(h->ah->cfg, av.batch_size, av.t_len, av.t_stride),
-                  make_lay(h->ah), w, epsilon, s};
+                  make_actor_step(h->a, pl.actor, m.replicated ? make_rep(&av) : rp, av.batch_size, pl.T, av.t_stride),
+                  epsilon, s};
 }
 
 // Mask sums (summed over the ranks in exchange mode), the critic inputs X, the target critic over every stored step
@@ -343,7 +220,7 @@ int ComaStep::targets() {
 // unroll beside it: the unroll reads nothing the critic writes, so it runs on the side stream in the CUs the chain
 // leaves idle. A refused launch clears chain_env and leaves the steps to critic_steps(), in this train() and after.
 int ComaStep::critic_chain() {
-  mq_handle* ah = h->ah;
+  mq_handle* ah = h->a.ah;
   if (pl.overlap) {
     MQ_HIP(ensure_side(ah));
     MQ_HIP(hipEventRecord(ah->ev_fork, s));   // before the chain: the side stream does not wait for it
@@ -387,7 +264,7 @@ int ComaStep::critic_chain() {
   // loud and leave the learner state unchanged (the restore)
   if (pl.overlap) {
     MQ_HIP(hipStreamWaitEvent(ah->side, ah->ev_fork, 0));
-    if ((rc = actor_forward(h, pl.actor, d, rpa, L, w, pl.actor_rows, ah->side))) return rc;
+    if ((rc = actor_forward(h->a, act, ah->side))) return rc;
     MQ_HIP(hipEventRecord(ah->ev_join, ah->side));
     actor_side = true;
   }
@@ -435,14 +312,15 @@ int ComaStep::critic_steps() {
 // output gradient, the weight gradients and their reduction.
 int ComaStep::actor() {
   int rc;
-  if (actor_side) MQ_HIP(hipStreamWaitEvent(s, h->ah->ev_join, 0));
-  else if ((rc = actor_forward(h, pl.actor, d, rpa, L, w, pl.actor_rows, s))) return rc;
+  const Actor& a = h->a;
+  if (actor_side) MQ_HIP(hipStreamWaitEvent(s, a.ah->ev_join, 0));
+  else if ((rc = actor_forward(a, act, s))) return rc;
   const float eps = epsilon, omeps = (float)(1.0 - (double)epsilon);
-  hipLaunchKernelGGL(coma_policy_kernel, dim3(pl.npol), dim3(256), 0, s, d, rpa, (const float*)w.Q,
-                     (const float*)h->qvals, pl.R, pl.qv_r0, eps, omeps, (int)(h->cfg.mask_before_softmax != 0), h->Ap,
-                     h->dL, h->pi, h->ppart);
+  hipLaunchKernelGGL(coma_policy_kernel, dim3(pl.npol), dim3(256), 0, s, act.d, act.rp, (const float*)act.w.Q,
+                     (const float*)h->qvals, pl.R, pl.qv_r0, eps, omeps, (int)(h->cfg.mask_before_softmax != 0), a.Ap,
+                     a.dL, a.pi, a.ppart);
   MQ_HIP(hipGetLastError());
-  return actor_backward(h, pl.actor, d, rpa, L, w, pl.actor_rows, pl.npol, s, &nnorm);
+  return actor_backward(a, act, pl.npol, s, &nnorm);
 }
 
 // Data parallel: the agent gradient + loss / mask sums over the ranks, then the norm partials of the summed gradient.
@@ -451,20 +329,21 @@ int ComaStep::actor() {
 int ComaStep::exchange() {
   if (!m.exchange && !m.replicated) return MQ_OK;
   const bool halt = m.replicated && chained;
+  const Actor& a = h->a;
   if (halt) {
     hipLaunchKernelGGL(coma_halt_to_sum_kernel, dim3(1), dim3(64), 0, s, (const int*)(h->cstate + 3),
-                       h->agrad + h->Pa + 7);
+                       a.agrad + a.Pa + 7);
     MQ_HIP(hipGetLastError());
   }
-  const int rc = mc_allreduce(h, h->agrad, h->Pa + MQ_NSUMS, s);
+  const int rc = mc_allreduce(h, a.agrad, a.Pa + MQ_NSUMS, s);
   if (rc) return rc;
   if (halt) {
-    hipLaunchKernelGGL(coma_sum_to_halt_kernel, dim3(1), dim3(64), 0, s, (const float*)(h->agrad + h->Pa + 7),
+    hipLaunchKernelGGL(coma_sum_to_halt_kernel, dim3(1), dim3(64), 0, s, (const float*)(a.agrad + a.Pa + 7),
                        h->cstate + 3);
     MQ_HIP(hipGetLastError());
   }
   nnorm = 256;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(nnorm), dim3(256), 0, s, (const float*)h->agrad, h->Pa, h->norm_part);
+  hipLaunchKernelGGL(sumsq_kernel, dim3(nnorm), dim3(256), 0, s, (const float*)a.agrad, a.Pa, a.norm_part);
   MQ_HIP(hipGetLastError());
   return MQ_OK;
 }
@@ -479,9 +358,10 @@ int ComaStep::apply_and_stats() {
     MQ_HIP(hipGetLastError());
   }
   const OptHP hp{c.lr, c.optim_alpha, c.optim_eps, c.grad_norm_clip, 1};
-  const int blocks = (int)std::min<int64_t>((h->Pa + 255) / 256, 1024);
-  hipLaunchKernelGGL(apply_kernel, dim3(blocks), dim3(256), 0, s, h->agent, h->agrad, h->asq, h->Pa,
-                     (const float*)h->norm_part, nnorm, hp, h->stats + 8,
+  const Actor& a = h->a;
+  const int blocks = (int)std::min<int64_t>((a.Pa + 255) / 256, 1024);
+  hipLaunchKernelGGL(apply_kernel, dim3(blocks), dim3(256), 0, s, a.agent, a.agrad, a.asq, a.Pa,
+                     (const float*)a.norm_part, nnorm, hp, h->stats + 8,
                      chained ? (const int*)(h->cstate + 3) : (const int*)nullptr);
   MQ_HIP(hipGetLastError());
   hipLaunchKernelGGL(coma_stats_kernel, dim3(1), dim3(64), 0, s, (const float*)h->crec, pl.T, (const int*)h->cstate,
@@ -539,51 +419,39 @@ int mc_create(const mc_config* cfg, mc_handle** out) {
   const mc_config& c = *cfg;
   if (c.n_actions < 1 || c.n_actions > 64) return set_err(MQ_ERR_ARG, "n_actions must be in [1, 64]");
   if (c.max_batch * c.n_agents > MQ_INLINE_IDS * 64) return set_err(MQ_ERR_ARG, "max_batch * n_agents too large");
+  std::unique_ptr<mc_handle> h(new mc_handle());   // a failure below frees it and the agent handle it owns
   const mq_config ac = agent_config(c, c.gamma);
-  mq_handle* ah = nullptr;
-  int rc = mq_create(&ac, &ah);
+  int rc = mq_create(&ac, &h->a.ah);
   if (rc) return rc;
-  std::unique_ptr<mc_handle> h(new mc_handle());   // owns ah from here: a failure below frees both
   h->cfg = c;
-  h->ah = ah;
-  h->I = ah->I;
-  for (int i = 0; i <= MQ_P_COUNT; ++i) h->aoff[i] = ah->off[i];
-  h->Pa = ah->P;
   const int n = c.n_agents, A = c.n_actions;
-  h->Kc = coma_k(c);
-  h->Kp = (h->Kc + 3) & ~3;
-  h->Ap = (A + 3) & ~3;
+  const int Kc = coma_k(c), Kp = (Kc + 3) & ~3;   // the critic's input width and its pitch
   mc_offsets(c, h->coff);
   h->Pc = h->coff[MC_P_COUNT];
 
   const int64_t Tp = c.max_seq, R = (int64_t)c.max_batch * n, T = Tp - 1;
-  const int64_t RTa = T * R;   // actor rows (T steps)
-  const int64_t red_tmp = kRedZ * ((int64_t)mq::H * h->I + mq::H) + kRedZ * h->ah->len_rnn +
-                          kRedZ * (A * mq::H + A) + kRedZ * 8;
-  const WsTable ws = {
-      {"X", Tp * R * h->Kp, &h->X},
+  WsTable ws = {
+      {"X", Tp * R * Kp, &h->X},
       {"H1t", Tp * R * CH, &h->H1t}, {"H2t", Tp * R * CH, &h->H2t},
       {"Qt", Tp * R * A, &h->Qt},
       {"tgt", T * R, &h->tgt}, {"msum", T, &h->msum},
       // three-launch l1 or chain phase A
-      {"H1p", coma_h1p_slices(h->Kc) * R * CH, &h->H1p},
+      {"H1p", coma_h1p_slices(Kc) * R * CH, &h->H1p},
       {"H1c", R * CH, &h->H1c}, {"H2c", R * CH, &h->H2c}, {"dH1c", R * CH, &h->dH1c}, {"dH2c", R * CH, &h->dH2c},
       {"dqc", R, &h->dqc}, {"actc", R, nullptr, &h->actc},
       {"qvals", T * R * A, &h->qvals},
       {"cpart", (int64_t)coma_heads((int)R) * 8, &h->cpart},
       // chain: 256 8-B granules + flags
-      {"cnorm", std::max<int64_t>(coma_wgrad_blocks(h->Kc, A), 1024), &h->cnorm},
+      {"cnorm", std::max<int64_t>(coma_wgrad_blocks(Kc, A), 1024), &h->cnorm},
       {"crec", T * 8, &h->crec},
       // shadow params / square_avg (the chain's gradient exchange: Pshadow)
       {"Pshadow", h->Pc, &h->Pshadow}, {"SQshadow", h->Pc, &h->SQshadow},
       {"cstate", 8, nullptr, &h->cstate},   // + the critic chain's sync words
-      {"dL", RTa * h->Ap, &h->dL}, {"dHo", RTa * mq::H, &h->dHo}, {"pi", RTa * A, &h->pi},
-      {"ppart", ((RTa + 3) / 4) * 8, &h->ppart},
-      {"slab_fc2", (int64_t)kNsplitMax * (A * mq::H + A), &h->slab_fc2},
-      {"red_tmp", red_tmp, &h->red_tmp},
-      {"norm_part", kNormPartMax, &h->norm_part},
-      {"Pbak", 2 * h->Pc, &h->Pbak},
   };
+  // the actor's rows behind the critic's: at the table's head the step measures 13 us slower (profiles/actor_host)
+  const WsTable actor_rows = actor_ws_rows(h->a, A, *h->a.ah, T * R);
+  ws.insert(ws.end(), actor_rows.begin(), actor_rows.end());
+  ws.push_back({"Pbak", 2 * h->Pc, &h->Pbak});
   if ((rc = ws_carve(h->ws, ws, "COMA workspace hipMalloc"))) return rc;
   h->chain_env = plan_int("coma_chain", 1) != 0;   // MQ_PLAN coma_chain=0: three launches per critic step
   int dev = 0;
@@ -601,8 +469,7 @@ int mc_destroy(mc_handle* h) {
 
 int mc_param_offsets(const mc_handle* h, int64_t* agent_offsets, int64_t* critic_offsets) {
   if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
-  if (agent_offsets)
-    for (int i = 0; i <= MQ_P_COUNT; ++i) agent_offsets[i] = h->aoff[i];
+  if (agent_offsets) (void)mq_param_offsets(h->a.ah, agent_offsets);
   if (critic_offsets)
     for (int i = 0; i <= MC_P_COUNT; ++i) critic_offsets[i] = h->coff[i];
   return MQ_OK;
@@ -612,15 +479,13 @@ int mc_bind(mc_handle* h, float* agent, float* agent_grad, float* agent_sq, floa
             float* critic_grad, float* critic_sq, float* stats) {
   if (!h || !agent || !agent_grad || !agent_sq || !critic || !target_critic || !critic_grad || !critic_sq || !stats)
     return set_err(MQ_ERR_ARG, "mc_bind: NULL pointer");
-  h->agent = agent; h->agrad = agent_grad; h->asq = agent_sq; h->critic = critic; h->tcritic = target_critic;
-  h->cgrad = critic_grad; h->csq = critic_sq; h->stats = stats;
-  // the agent handle: online = target = the agent params (the actor has no target net); stats land at stats + 8
-  return mq_bind(h->ah, agent, agent, agent_grad, agent_sq, stats + 8, nullptr);
+  h->critic = critic; h->tcritic = target_critic; h->cgrad = critic_grad; h->csq = critic_sq; h->stats = stats;
+  return actor_bind(h->a, agent, agent_grad, agent_sq, stats);
 }
 
 int mc_train_step(mc_handle* h, const mq_replay* batch, float epsilon, void* stream) {
-  if (!h || !h->agent) return set_err(MQ_ERR_STATE, "mc_train_step before mc_bind");
-  int rc = check_batch(h->ah, batch);
+  if (!h || !h->a.agent) return set_err(MQ_ERR_STATE, "mc_train_step before mc_bind");
+  int rc = check_batch(h->a.ah, batch);
   if (rc) return rc;
   const bool repl = h->shard_hi > h->shard_lo;
   if (repl && (h->shard_lo < 0 || h->shard_hi > batch->batch_size))
@@ -635,6 +500,7 @@ int mc_train_step(mc_handle* h, const mq_replay* batch, float epsilon, void* str
                       h->shard_lo, h->shard_hi};
   const ComaPlan pl = coma_plan(h->cfg, batch->batch_size, batch->t_len, h->num_cu, mode);
   if (pl.refused) return set_err(MQ_ERR_ARG, pl.refused);
+  if ((rc = actor_prepare(h->a, pl.actor, "COMA plan exceeds the workspace"))) return rc;
   ComaStep st = make_coma_step(h, batch, pl, mode, epsilon, (hipStream_t)stream);
   if ((rc = st.targets()) || (rc = st.critic_chain()) || (rc = st.critic_steps()) || (rc = st.actor()) ||
       (rc = st.exchange()) || (rc = st.apply_and_stats()))
@@ -748,7 +614,7 @@ int mc_copy_intermediate(mc_handle* h, int which, float* dst, int64_t* count, vo
   switch (which) {
     case 0: src = h->qvals; cnt = TRc * h->cfg.n_actions; break;
     case 1: src = h->tgt; cnt = TRc; break;
-    case 2: src = h->pi; cnt = TR * h->cfg.n_actions; break;
+    case 2: src = h->a.pi; cnt = TR * h->cfg.n_actions; break;
     default: return set_err(MQ_ERR_ARG, "unknown COMA intermediate id");
   }
   if (count) *count = cnt;

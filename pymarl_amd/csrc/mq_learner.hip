@@ -31,10 +31,11 @@
 // learner_layout.hpp (parameter layout and workspace sizes from the config), step_plan.hpp and reduce_plan.hpp (what a
 // step launches, decided without a HIP call), learner_handle.hpp (mq_handle, batch checks), step_launch.hpp (the
 // launches), optim_host.hpp (Adam's host side, and launch_reduce: the two-pass reduction's launcher outside Step),
-// actor_plan.hpp (what the policy-gradient actor launches, for the three learners below), coma_plan.hpp (what a COMA
-// step launches, decided without a HIP call) and coma_host.hpp (the COMA learner: its handle, the shared actor, the
-// step's phases), a2c_host.hpp (the actor-critic learner, with a2c_plan.hpp and a2c_kernels.hpp), ppo_host.hpp (its
-// PPO step). This file holds the C ABI.
+// actor_plan.hpp (the policy-gradient actor of the three learners below without a HIP call: what a handle holds of it,
+// its workspace rows, what it launches, its reduction) and actor_host.hpp (its launches), coma_plan.hpp (what a COMA
+// step launches, decided without a HIP call) and coma_host.hpp (the COMA learner: its handle, the step's phases),
+// a2c_host.hpp (the actor-critic learner, with a2c_plan.hpp and a2c_kernels.hpp), ppo_host.hpp (its PPO step). This
+// file holds the C ABI.
 #include <algorithm>
 #include <cstring>
 #include <memory>

@@ -9,16 +9,16 @@
 namespace {
 
 int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStream_t s) {
-  mq_handle* ah = h->ah;
+  const Actor& a = h->a;
   const ma_config& c = h->cfg;
   const int n = c.n_agents, Hc = h->Hc, E = h->pp.epochs;
   const int B = batch->batch_size, Tp = batch->t_len, T = Tp - 1, R = B * n;
   const Rep rp = make_rep(batch);
   const ADims cd = ma_dims(c, B, Tp, batch->t_stride);
   ma_plan pl;
-  ActorPlan ap;
+  ActorStep act;
   int rc, hoisted = 0;
-  if ((rc = ma_step_plan(h, B, Tp, &pl, &ap))) return rc;
+  if ((rc = ma_step_plan(h, batch, rp, &pl, &act))) return rc;
   const int64_t RT = (int64_t)T * R, RTp = (int64_t)Tp * R;
   const float lo = (float)(1.0 - (double)h->pp.eps_clip), hi = (float)(1.0 + (double)h->pp.eps_clip);
 
@@ -32,19 +32,15 @@ int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStr
                      (float*)nullptr, R, n, 0);
   MQ_HIP(hipGetLastError());
   hoisted += 4;
-  const Dims d = mq::make_dims(ah->cfg, B, T, batch->t_stride);   // d.Tp = T: d.RT() = T R
   // ---- once: the rewards standardised (the running statistics merge the batch once), the n-step returns
   if ((rc = ma_returns(h, cd, rp, pl, s))) return rc;
   hoisted += h->rew_state ? 2 : 0;
   // ---- once: both gradient buffers as the caller left them (an empty batch puts them back after every epoch)
-  const int64_t na = h->Pa + MQ_NSUMS, nc = h->Pc + MA_NTAIL;
-  MQ_HIP(hipMemcpyAsync(h->gbak, h->agrad, (size_t)na * sizeof(float), hipMemcpyDeviceToDevice, s));
+  const int64_t na = a.Pa + MQ_NSUMS, nc = h->Pc + MA_NTAIL;
+  MQ_HIP(hipMemcpyAsync(h->gbak, a.agrad, (size_t)na * sizeof(float), hipMemcpyDeviceToDevice, s));
   MQ_HIP(hipMemcpyAsync(h->gbak + na, h->cgrad, (size_t)nc * sizeof(float), hipMemcpyDeviceToDevice, s));
   hoisted += 3;
 
-  const Lay L = make_lay(ah);
-  Work w = ah->w;
-  w.dHo = h->dHo;
   const int mbs = (int)(c.mask_before_softmax != 0);
   for (int k = 0; k < E; ++k) {
     // ---- critic: V of the current parameters over t < T, td against the fixed returns
@@ -58,30 +54,25 @@ int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStr
                        h->cpart);
     MQ_HIP(hipGetLastError());
     // ---- actor forward and the clipped surrogate (epoch 0 writes the old log-probabilities)
-    if ((rc = actor_forward(h, ap, d, rp, L, w, RT, s))) return rc;
-    if (k == 0)
-      hipLaunchKernelGGL(ppo_policy_kernel<true>, dim3(pl.policy_blocks), dim3(256), 0, s, d, rp, (const float*)w.Q,
-                         (const float*)h->td, c.entropy_coef, lo, hi, mbs, h->Ap, h->old_lp, h->ratio, h->dL, h->pi,
-                         h->ppart);
-    else
-      hipLaunchKernelGGL(ppo_policy_kernel<false>, dim3(pl.policy_blocks), dim3(256), 0, s, d, rp, (const float*)w.Q,
-                         (const float*)h->td, c.entropy_coef, lo, hi, mbs, h->Ap, h->old_lp, h->ratio, h->dL, h->pi,
-                         h->ppart);
+    if ((rc = actor_forward(a, act, s))) return rc;
+    hipLaunchKernelGGL(k == 0 ? ppo_policy_kernel<true> : ppo_policy_kernel<false>, dim3(pl.policy_blocks), dim3(256), 0,
+                       s, act.d, rp, (const float*)act.w.Q, (const float*)h->td, c.entropy_coef, lo, hi, mbs, a.Ap,
+                       h->old_lp, h->ratio, a.dL, a.pi, a.ppart);
     MQ_HIP(hipGetLastError());
     // ---- both backwards, then both applies (Adam step number adam_step + k), then the epoch's stats row
     int nnorm_c, nnorm_a;
     if ((rc = ma_critic_dw(h, pl, RT, s)) || (rc = ma_critic_reduce(h, pl, s, &nnorm_c)) ||
-        (rc = actor_backward(h, ap, d, rp, L, w, RT, pl.policy_blocks, s, &nnorm_a, h->slab_ffn)) ||
+        (rc = actor_backward(a, act, pl.policy_blocks, s, &nnorm_a)) ||
         (rc = ma_gate_apply(h, nnorm_c, nnorm_a, adam_step + k, s)))
       return rc;
     hipLaunchKernelGGL(ppo_stats_kernel, dim3(1), dim3(64), 0, s, (const float*)h->stats,
-                       (const float*)(h->agrad + h->Pa), (const int*)h->halt, h->pp.epoch_stats + (int64_t)k * MA_NSTATS);
+                       (const float*)(a.agrad + a.Pa), (const int*)h->halt, h->pp.epoch_stats + (int64_t)k * MA_NSTATS);
     MQ_HIP(hipGetLastError());
   }
   pl.epochs = E;
   pl.hoisted = hoisted;
   h->last = pl;
-  h->last_ffn = a2c_actor_report(ap);
+  h->last_ffn = a2c_actor_report(act.ap);
   h->last_T = T;
   h->last_R = R;
   return MQ_OK;

@@ -11,7 +11,8 @@ or two checkouts' Python over one build (a refactor of the learners' Python).
 Cases, each at fixed seeds: the golden COMA cases coma_tiny_masked and coma_cfg5 (MMM2's shape), each on the persistent
 chain and under MQ_PLAN=coma_chain=0 (the three-launch critic step); the actor-critic learner on tests/a2c_ref.py's
 `split` row (544 rows: every split-K weight gradient has two slices); the PPO learner on tests/ppo_ref.py's `split` row
-at two epochs. After every train() it hashes every buffer the learner bound (parameters, square averages / Adam
+at two epochs; both again with the feed-forward actor (tests/a2c_ffn_ref.py's `split` row and PPOFFCase("split"),
+without a checkpoint). After every train() it hashes every buffer the learner bound (parameters, square averages / Adam
 moments, both gradient buffers with their tails, the target critic, the stats) and every *_copy_intermediate array.
 The Q learner on the goldens' tiny shapes: tiny_qmix / tiny_vdn / tiny_iql, tiny_qmix_adam (optimizer: adam),
 tiny_qmix_h2 (the two-layer hypernet), tiny_qmix with the soft target update and standardised rewards, with TD(lambda)
@@ -167,11 +168,12 @@ def coma_case(name, chain, ckpt=False):
 A2C_BUFFERS = ("_agent", "_agrad", "_asq", "_am", "_critic", "_tcritic", "_cgrad", "_csq", "_cm", "_stats", "rew_ms")
 
 
-def a2c_case():
-    from tests import a2c_ref
+def a2c_case(ffn=False):
+    from tests import a2c_ffn_ref, a2c_ref
     from tests.a2c_helpers import build_a2c
-    c = a2c_ref.A2CCase("split")
-    _, buf, _, learner, _ = build_a2c(c)
+    c = a2c_ffn_ref.A2CFFCase("split") if ffn else a2c_ref.A2CCase("split")
+    over = dict(use_rnn=False) if ffn else {}
+    _, buf, _, learner, _ = build_a2c(c, **over)
     out = []
     for k in range(STEPS):
         b = buf.sample(c.B)
@@ -179,15 +181,17 @@ def a2c_case():
         d = digests(learner, A2C_BUFFERS, (0, 1, 2, 3, 4))
         d["plan"] = learner.last_plan()
         out.append(d)
-    checkpoint("a2c/split", learner, build_a2c(c)[3], A2C_BUFFERS)
+    if not ffn:
+        checkpoint("a2c/split", learner, build_a2c(c)[3], A2C_BUFFERS)
     return out
 
 
-def ppo_case():
-    from tests import ppo_ref
+def ppo_case(ffn=False):
+    from tests import a2c_ffn_ref, ppo_ref
     from tests.ppo_helpers import build_ppo
-    c = ppo_ref.PPOCase("split")
-    _, buf, _, learner, _ = build_ppo(c, epochs=2)
+    c = a2c_ffn_ref.PPOFFCase("split") if ffn else ppo_ref.PPOCase("split")
+    over = dict(epochs=2, use_rnn=False) if ffn else dict(epochs=2)
+    _, buf, _, learner, _ = build_ppo(c, **over)
     out = []
     for k in range(STEPS):
         b = buf.sample(c.B)
@@ -195,7 +199,8 @@ def ppo_case():
         d = digests(learner, A2C_BUFFERS + ("_estats",), (0, 1, 2, 3, 4, 5, 6))
         d["plan"] = learner.last_plan()
         out.append(d)
-    checkpoint("ppo/split_epochs2", learner, build_ppo(c, epochs=2)[3], A2C_BUFFERS)
+    if not ffn:
+        checkpoint("ppo/split_epochs2", learner, build_ppo(c, **over)[3], A2C_BUFFERS)
     return out
 
 
@@ -234,6 +239,10 @@ def main():
     res["a2c/split"] = a2c_case()
     np.random.seed(0)
     res["ppo/split_epochs2"] = ppo_case()
+    np.random.seed(0)
+    res["a2c_ffn/split"] = a2c_case(ffn=True)
+    np.random.seed(0)
+    res["ppo_ffn/split_epochs2"] = ppo_case(ffn=True)
     for name in Q_CASES:
         res["q/" + name] = q_case(name, ckpt=name == "tiny_qmix_soft_rewnorm")
     res["q/tiny_qmix_per"] = per_case()
