@@ -45,7 +45,11 @@ typedef struct ma_config {
   float lr, optim_alpha, optim_eps, grad_norm_clip;   /* one lr for both optimisers */
   const float* gamma_pow;          /* HOST pointer, q_nstep + 2 floats: g[k] = float32(gamma ** k); ma_create copies it */
   int32_t max_batch, max_seq;
-  int32_t agent;                   /* MQ_AGENT_*: 0 (a zeroed field) the GRU agent, MQ_AGENT_FFN the feed-forward one */
+  int32_t agent;                   /* MQ_AGENT_*: 0 (a zeroed field) the GRU agent, MQ_AGENT_FFN the feed-forward one,
+                                      MQ_AGENT_FFN_NS one feed-forward agent per agent index (epymarl's agent: rnn_ns
+                                      under use_rnn: False): the agent buffers of ma_bind are then
+                                      n_agents blocks of Pa1 floats, block g agent g's in the feed-forward order, and
+                                      agent_offsets of ma_param_offsets describe one block (its last entry is Pa1) */
 } ma_config;
 
 /* Adam in RMSprop's place for both optimisers: the first-moment buffers [Pa] / [Pc] (the second moments live where
@@ -100,6 +104,11 @@ typedef struct ma_actor {
   int32_t ffn_blocks;     /* ffn_actor_bwd_kernel's workgroups = its slabs (MQ_PLAN ffn_actor_blocks=<n> lowers the cap) */
   int32_t ffn_tiles_per_block;   /* tiles each of them walks, in order (the last one the rest) */
   int32_t ffn_fwd_lds;    /* ffn_actor_fwd_kernel's dynamic LDS, bytes: 87040 when W1 is streamed in K chunks */
+  /* MQ_AGENT_FFN_NS (0 otherwise): the grouped plan per agent. ffn_tiles and ffn_blocks above are then n_agents times
+   * the first two, and ffn_tiles_per_block the tiles a workgroup walks of its one agent */
+  int32_t ns_tiles_per_agent;    /* 64-row tiles of an agent's T * B rows */
+  int32_t ns_blocks_per_agent;   /* ffn_actor_ns_bwd_kernel's workgroups per agent = whole-gradient slabs */
+  int32_t ns_slices_per_agent;   /* split-K slices of an agent's [dW1 | db1]: slice s is the rows of workgroup s's tiles */
 } ma_actor;
 
 typedef struct ma_handle ma_handle;
@@ -138,6 +147,13 @@ int ma_critic_forward(const float* critic, const ma_config* cfg, const mq_replay
  * After a PPO step 1, 3 and 4 hold the last epoch's values, and 5 = old, epoch 0's log pi_u [T][B*n];
  * 6 = the last epoch's ratio [T][B*n]. */
 int ma_copy_intermediate(ma_handle* h, int which, float* dst, int64_t* count, void* stream);
+/* One acting step of the non-shared actor (cfg->agent = MQ_AGENT_FFN_NS) outside train(): the grouped forward kernel
+ * over the batch_size * n_agents rows of stored step t. agent: n_agents blocks of parameters. logits
+ * [batch_size][n_agents][n_actions]; hidden [n_agents][batch_size][64] (agent-major), h = relu(rnn(x1)); workspace:
+ * ma_actor_ns_forward_workspace(cfg, batch_size) floats of device memory. cfg->gamma_pow is not read. */
+int64_t ma_actor_ns_forward_workspace(const ma_config* cfg, int32_t batch_size);
+int ma_actor_ns_forward(const float* agent, const ma_config* cfg, const mq_replay* batch, int32_t t, float* logits,
+                        float* hidden, float* workspace, void* stream);
 int ma_last_plan(const ma_handle* h, ma_plan* out);
 int ma_last_actor(const ma_handle* h, ma_actor* out);
 

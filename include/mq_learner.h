@@ -69,8 +69,9 @@ enum {
  * buffer's order is fc1.weight, fc1.bias, rnn.weight, rnn.bias, fc2.weight, fc2.bias, <mixer>, and the four GRU
  * entries MQ_P_RNN_* report offset = total (tensors of zero floats), as the absent hypernet entries do. With the GRU
  * the two FFN entries report offset = total. They sit after MQ_P_HWF_B2 so that every earlier entry keeps its
- * number. */
-enum { MQ_AGENT_GRU = 0, MQ_AGENT_FFN = 1 };
+ * number. MQ_AGENT_FFN_NS is ma_config.agent's alone (include/ma_a2c.h): one feed-forward agent per agent index;
+ * mq_create refuses it as any other unknown value. */
+enum { MQ_AGENT_GRU = 0, MQ_AGENT_FFN = 1, MQ_AGENT_FFN_NS = 2 };
 
 typedef struct mq_config {
   int32_t n_agents, n_actions, obs_dim, state_dim;

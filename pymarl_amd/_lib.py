@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MQ_LEARNER_LIB", os.path.join(HERE, "lib", "libmq_learner.so"))
 
 MIXER_NONE, MIXER_VDN, MIXER_QMIX = 0, 1, 2
-AGENT_GRU, AGENT_FFN = 0, 1   # MQ_AGENT_*
+AGENT_GRU, AGENT_FFN, AGENT_FFN_NS = 0, 1, 2   # MQ_AGENT_* (AGENT_FFN_NS: ma_config.agent only)
 NSUMS = 8
 NSTATS = 8
 PARAM_NAMES = [
@@ -46,7 +46,7 @@ EXPORTS = [
 MA_EXPORTS = [
     "ma_create", "ma_destroy", "ma_param_offsets", "ma_bind", "ma_set_adam", "ma_set_reward_norm", "ma_train_step",
     "ma_update_targets", "ma_critic_forward_workspace", "ma_critic_forward", "ma_copy_intermediate", "ma_last_plan",
-    "ma_set_ppo", "ma_last_actor",
+    "ma_set_ppo", "ma_last_actor", "ma_actor_ns_forward_workspace", "ma_actor_ns_forward",
 ]
 
 # mc_allreduce_fn (include/mc_coma.h): int (*)(float* buf, int64_t count, void* stream, void* ctx)
@@ -116,7 +116,8 @@ class MAConfig(ctypes.Structure):
         ("entropy_coef", ctypes.c_float), ("lr", ctypes.c_float), ("optim_alpha", ctypes.c_float),
         ("optim_eps", ctypes.c_float), ("grad_norm_clip", ctypes.c_float), ("gamma_pow", ctypes.c_void_p),
         ("max_batch", ctypes.c_int32), ("max_seq", ctypes.c_int32),
-        ("agent", ctypes.c_int32),   # AGENT_GRU (0, a zeroed field) or AGENT_FFN: the feed-forward actor
+        # AGENT_GRU (0, a zeroed field), AGENT_FFN: the feed-forward actor, AGENT_FFN_NS: one such actor per agent
+        ("agent", ctypes.c_int32),
     ]
 
 
@@ -145,9 +146,11 @@ class MAPlan(ctypes.Structure):
 
 
 class MAActor(ctypes.Structure):
-    """ma_actor: what the last step launched for its actor; all 0 with the GRU agent."""
+    """ma_actor: what the last step launched for its actor; all 0 with the GRU agent, the ns_* items 0 unless the
+    actor is the non-shared one."""
     _fields_ = [(k, ctypes.c_int32) for k in ("agent", "ffn_tiles", "ffn_blocks", "ffn_tiles_per_block",
-                                               "ffn_fwd_lds")]
+                                               "ffn_fwd_lds", "ns_tiles_per_agent", "ns_blocks_per_agent",
+                                               "ns_slices_per_agent")]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -274,6 +277,9 @@ def load(required=True):
         "ma_last_plan": ([vp, ctypes.POINTER(MAPlan)], ctypes.c_int),
         "ma_last_actor": ([vp, ctypes.POINTER(MAActor)], ctypes.c_int),
         "ma_set_ppo": ([vp, ctypes.POINTER(MAPpo)], ctypes.c_int),
+        "ma_actor_ns_forward_workspace": ([ctypes.POINTER(MAConfig), i32], i64),
+        "ma_actor_ns_forward": ([vp, ctypes.POINTER(MAConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp, vp],
+                                ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

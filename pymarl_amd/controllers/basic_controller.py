@@ -34,6 +34,8 @@ class BasicMAC:
         self.args = args
         input_shape = self._get_input_shape(scheme)
         self._build_agents(input_shape)
+        if getattr(self.agent, "non_shared", False) and type(self) is BasicMAC:
+            raise ValueError("agent: rnn_ns needs mac: non_shared_mac: basic_mac shares one agent's parameters.")
         self.agent_output_type = args.agent_output_type
         if not use_rnn_config(args) and getattr(args, "learner", None) == "coma_learner":
             raise ValueError("use_rnn: False is not supported with learner coma_learner: COMA's actor is the GRU agent")

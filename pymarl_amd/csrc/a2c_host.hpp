@@ -48,8 +48,8 @@ int ma_check_config(const ma_config& c, bool train) {
   if (c.n_agents < 1 || c.n_agents > 64) return set_err(MQ_ERR_ARG, "n_agents must be in [1, 64]");
   if (c.n_actions < 1 || c.n_actions > 64) return set_err(MQ_ERR_ARG, "n_actions must be in [1, 64]");
   if (c.obs_dim < 1 || c.state_dim < 1) return set_err(MQ_ERR_ARG, "obs_dim / state_dim must be positive");
-  if (c.agent != MQ_AGENT_GRU && c.agent != MQ_AGENT_FFN)
-    return set_err(MQ_ERR_ARG, "agent must be MQ_AGENT_GRU (0) or MQ_AGENT_FFN (1)");
+  if (c.agent != MQ_AGENT_GRU && c.agent != MQ_AGENT_FFN && c.agent != MQ_AGENT_FFN_NS)
+    return set_err(MQ_ERR_ARG, "agent must be MQ_AGENT_GRU (0), MQ_AGENT_FFN (1) or MQ_AGENT_FFN_NS (2)");
   if (!train) return MQ_OK;
   if (c.q_nstep < 1) return set_err(MQ_ERR_ARG, "q_nstep must be >= 1");
   if (!(c.entropy_coef >= 0.0f)) return set_err(MQ_ERR_ARG, "entropy_coef must be >= 0");
@@ -246,12 +246,62 @@ int ma_critic_forward(const float* critic, const ma_config* cfg, const mq_replay
   return MQ_OK;
 }
 
+int64_t ma_actor_ns_forward_workspace(const ma_config* cfg, int32_t batch_size) {
+  if (!cfg || batch_size < 1) return -1;
+  const int64_t I = cfg->obs_dim + (cfg->obs_last_action ? cfg->n_actions : 0) + (cfg->obs_agent_id ? cfg->n_agents : 0);
+  const int64_t rows = (int64_t)batch_size * cfg->n_agents;
+  return align_up(rows * mq::H) + align_up(rows * I);   // X1, XIN
+}
+
+int ma_actor_ns_forward(const float* agent, const ma_config* cfg, const mq_replay* batch, int32_t t, float* logits,
+                        float* hidden, float* workspace, void* stream) {
+  if (!agent || !cfg || !batch || !logits || !hidden || !workspace)
+    return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: NULL pointer");
+  int rc = ma_check_config(*cfg, false);
+  if (rc) return rc;
+  if (cfg->agent != MQ_AGENT_FFN_NS) return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: agent must be MQ_AGENT_FFN_NS");
+  if (!batch->obs || !batch->actions || !batch->filled)
+    return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: batch needs obs, actions and filled");
+  if (batch->batch_size < 1 || batch->t_len < 1 || batch->t_len > batch->t_stride)
+    return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: bad batch dimensions");
+  if (t < 0 || t >= batch->t_len) return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: t outside the batch");
+  if ((int64_t)batch->batch_size * cfg->n_agents >= (1LL << 31))
+    return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: batch too large for 32-bit row indices");
+  if ((rc = check_ids(batch))) return rc;
+  if (batch->ep_ids_host && batch->batch_size > MQ_INLINE_IDS && !batch->ep_ids)
+    return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: more than MQ_INLINE_IDS episodes need device ids");
+  hipStream_t s = (hipStream_t)stream;
+  const int B = batch->batch_size, n = cfg->n_agents;
+  mq_config ac = agent_config(*cfg, 0.0f, cfg->agent);
+  ac.max_batch = B;
+  ac.max_seq = 2;
+  const Layout y = make_layout(ac);
+  const Dims d = mq::make_dims(ac, B, 1, batch->t_stride);
+  const size_t lds = ffn_actor_fwd_lds_bytes(d.I);
+  if (lds > kFfnActorLdsMax) return set_err(MQ_ERR_ARG, "the feed-forward actor's forward exceeds the LDS");
+  MQ_LDS(ffn_actor_ns_fwd_kernel, lds);
+  MQ_HIP(hipFuncSetAttribute((const void*)ffn_actor_ns_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)kFfnActorLdsMax));
+  float* X1 = workspace;
+  float* XIN = X1 + align_up((int64_t)B * n * mq::H);
+  const FfnNsFwd p = ffn_ns_fwd_args(d, make_rep(batch), agent, y.P, y.off, X1, hidden, logits, XIN, B, t);
+  hipLaunchKernelGGL(ffn_actor_ns_fwd_kernel, dim3(p.tpa, n), dim3(256), lds, s, p);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
 int ma_create(const ma_config* cfg, ma_handle** out) {
   if (!cfg || !out) return set_err(MQ_ERR_ARG, "NULL argument");
   const ma_config& c = *cfg;
   int rc = ma_check_config(c, true);
   if (rc) return rc;
   if (c.max_batch * c.n_agents > MQ_INLINE_IDS * 64) return set_err(MQ_ERR_ARG, "max_batch * n_agents too large");
+  const int ffn_cap = plan_int("ffn_actor_blocks", 0);   // the one read of this MQ_PLAN item per handle
+  const bool grouped = c.agent == MQ_AGENT_FFN_NS;
+  // the grouped backward gives every agent a workgroup of its own: n of them must fit the cap
+  if (grouped && c.n_agents > (ffn_cap > 0 ? std::min(ffn_cap, kFfnActorBlocks) : kFfnActorBlocks))
+    return set_err(MQ_ERR_ARG, "n_agents " + std::to_string(c.n_agents) + " exceeds the non-shared actor's workgroup " +
+                                   "cap (MQ_PLAN ffn_actor_blocks)");
   std::unique_ptr<ma_handle> h(new ma_handle());   // a failure below frees it and the agent handle it owns
   const mq_config ac = agent_config(c, c.gamma_pow[1], c.agent);   // (ma_check_config: gamma_pow is not NULL)
   if ((rc = mq_create(&ac, &h->a.ah))) return rc;
@@ -267,7 +317,7 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
   const int64_t Tp = c.max_seq, R = (int64_t)c.max_batch * n, T = Tp - 1, RT = T * R;
   h->ns_max = a2c_ns_max(RT);
   h->ndv_max = (int)((RT + A2C_DV_ROWS - 1) / A2C_DV_ROWS);
-  h->a.ffn_cap = plan_int("ffn_actor_blocks", 0);   // the one read of this MQ_PLAN item per handle
+  h->a.ffn_cap = ffn_cap;
   const int64_t lw1 = (int64_t)Hc * h->K + Hc, lw2 = (int64_t)Hc * Hc + Hc, lw3 = Hc + 1;
   const int64_t cred_tmp = kRedZ * (lw1 + lw2 + lw3 + 8);
   float* rbak_f = nullptr;
@@ -284,7 +334,11 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
       {"cred_tmp", cred_tmp, &h->cred_tmp}, {"cnorm_part", kNormPartMax, &h->cnorm_part},
       {"halt", 8, nullptr, &h->halt},
   };
-  const WsTable actor_rows = actor_ws_rows(h->a, c.n_actions, *h->a.ah, RT);
+  const WsTable actor_rows = actor_ws_rows(h->a, c.n_actions, *h->a.ah, RT, grouped ? n : 0);
+  // the grouped actor's one reduction region is the whole gradient: its norm partials, with the loss sums' block
+  if (grouped && (h->a.Pa + 255) / 256 + 1 > kNormPartMax)
+    return set_err(MQ_ERR_ARG, "the non-shared actor's " + std::to_string(h->a.Pa) +
+                                   " parameters are too many for the norm partial buffer");
   ws.insert(ws.end(), actor_rows.begin(), actor_rows.end());
   ws.insert(ws.end(), {
       {"old_lp", RT, &h->old_lp}, {"ratio", RT, &h->ratio},

@@ -50,7 +50,7 @@ inline ma_plan a2c_plan(const ma_config& c, int B, int t_len, bool reward_norm, 
   if (actor) *actor = ap;
   p.ns_aw1 = ap.ns_w1;
   p.ns_aw2 = ap.ns_w2;
-  p.bwd_blocks = c.agent == MQ_AGENT_FFN ? ap.ffn_blocks : ap.nblk_bwd;
+  p.bwd_blocks = c.agent == MQ_AGENT_GRU ? ap.nblk_bwd : ap.ffn_blocks;
   p.reward_norm = reward_norm ? 1 : 0;
   p.adam = adam ? 1 : 0;
   return p;
@@ -58,7 +58,8 @@ inline ma_plan a2c_plan(const ma_config& c, int B, int t_len, bool reward_norm, 
 
 // What ma_last_actor reports of an ActorPlan.
 inline ma_actor a2c_actor_report(const ActorPlan& ap) {
-  return ma_actor{ap.agent, ap.ffn_tiles, ap.ffn_blocks, ap.ffn_tpb, (int32_t)ap.ffn_fwd_lds};
+  return ma_actor{ap.agent, ap.ffn_tiles, ap.ffn_blocks, ap.ffn_tpb, (int32_t)ap.ffn_fwd_lds,
+                  ap.ns_tpa, ap.ns_bpa, ap.agent == MQ_AGENT_FFN_NS ? ap.ns_w1 : 0};
 }
 
 }  // namespace mq

@@ -19,19 +19,31 @@ int actor_bind(Actor& a, float* agent, float* agent_grad, float* agent_sq, float
 // Before a step's first launch: the plan's slabs against actor_ws_rows' (`exceeds`: the learner's error text), the
 // feed-forward kernels' LDS against the CU's. That LDS is past a launch's default: the attributes are raised once.
 int actor_prepare(Actor& a, const ActorPlan& ap, const char* exceeds) {
-  if (ap.ns_w2 > kNsplitMax || ap.ffn_blocks > a.ffn_slabs_max) return set_err(MQ_ERR_STATE, exceeds);
-  if (ap.agent != MQ_AGENT_FFN) return MQ_OK;
+  const bool grouped = ap.agent == MQ_AGENT_FFN_NS;   // its slabs are per agent (ns_bpa of them), not ffn_blocks
+  if (ap.ns_w2 > kNsplitMax || (grouped ? ap.ns_bpa : ap.ffn_blocks) > a.ffn_slabs_max)
+    return set_err(MQ_ERR_STATE, exceeds);
+  if (ap.agent != MQ_AGENT_FFN && !grouped) return MQ_OK;
   if (ap.ffn_fwd_lds > kFfnActorLdsMax) return set_err(MQ_ERR_ARG, "the feed-forward actor's forward exceeds the LDS");
-  MQ_LDS(ffn_actor_fwd_kernel, ap.ffn_fwd_lds);
-  MQ_LDS(ffn_actor_bwd_kernel, kFfnActorBwdLds);
-  if (!a.ffn_attr) {
-    MQ_HIP(hipFuncSetAttribute((const void*)ffn_actor_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)kFfnActorLdsMax));
-    MQ_HIP(hipFuncSetAttribute((const void*)ffn_actor_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)kFfnActorLdsMax));
+  const void* fwd = grouped ? (const void*)ffn_actor_ns_fwd_kernel : (const void*)ffn_actor_fwd_kernel;
+  const void* bwd = grouped ? (const void*)ffn_actor_ns_bwd_kernel : (const void*)ffn_actor_bwd_kernel;
+  if (const int rc = lds_fits(fwd, ap.ffn_fwd_lds, grouped ? "ffn_actor_ns_fwd_kernel" : "ffn_actor_fwd_kernel"))
+    return rc;
+  if (const int rc = lds_fits(bwd, kFfnActorBwdLds, grouped ? "ffn_actor_ns_bwd_kernel" : "ffn_actor_bwd_kernel"))
+    return rc;
+  if (!a.ffn_attr) {   // a handle has one agent kind: these are its two kernels
+    MQ_HIP(hipFuncSetAttribute(fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFfnActorLdsMax));
+    MQ_HIP(hipFuncSetAttribute(bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFfnActorLdsMax));
     a.ffn_attr = true;
   }
   return MQ_OK;
+}
+
+// The grouped forward's argument block over TB rows per agent whose t = 0 is stored step t0 (off: one agent's offsets).
+FfnNsFwd ffn_ns_fwd_args(const Dims& d, const Rep& rp, const float* P, int64_t Pa1, const int64_t* off, float* X1,
+                         float* Hh, float* Q, float* XIN, int TB, int t0) {
+  return FfnNsFwd{d, rp, P, Pa1, off[MQ_P_FC1_W], off[MQ_P_FC1_B], off[MQ_P_FFN_W], off[MQ_P_FFN_B], off[MQ_P_FC2_W],
+                  off[MQ_P_FC2_B], X1, Hh, Q, XIN, TB, (TB + FA_ROWS - 1) / FA_ROWS, t0,
+                  ffn_actor_w1_resident(d.I) ? 1 : 0};
 }
 
 // One step's actor: its plan and the argument blocks its launches take.
@@ -57,6 +69,12 @@ int actor_forward(const Actor& a, const ActorStep& st, hipStream_t s) {
   const auto& [ap, d, rp, L, w, RT] = st;
   const int64_t* off = a.ah->off;
   const float* Pa = a.agent;
+  if (ap.agent == MQ_AGENT_FFN_NS) {   // grid (workgroups per agent, agent): a workgroup loads one agent's weights
+    const FfnNsFwd p = ffn_ns_fwd_args(d, rp, Pa, a.Pa1, off, w.X1, w.Hs, w.Q, w.XIN, (int)(RT / d.n), 0);
+    hipLaunchKernelGGL(ffn_actor_ns_fwd_kernel, dim3(ap.ns_fpa, d.n), dim3(256), ap.ffn_fwd_lds, s, p);
+    MQ_HIP(hipGetLastError());
+    return MQ_OK;
+  }
   if (ap.agent == MQ_AGENT_FFN) {
     const FfnActorFwd p{d, rp, Pa, off[MQ_P_FC1_W], off[MQ_P_FC1_B], off[MQ_P_FFN_W], off[MQ_P_FFN_B], off[MQ_P_FC2_W],
                         off[MQ_P_FC2_B], w.X1, w.Hs, w.Q, w.XIN, RT, ap.ffn_tiles, ap.ffn_resident};
@@ -88,6 +106,17 @@ int actor_backward(const Actor& a, const ActorStep& st, int npol, hipStream_t s,
   const auto& [ap, d, rp, L, w, RT] = st;
   const mq_handle* ah = a.ah;
   const float* Pa = a.agent;
+  if (ap.agent == MQ_AGENT_FFN_NS) {
+    // every (slab, agent) block is written whole: [dWr .. db2] by workgroup (j, g), [dW1 | db1] by slice (g, j)
+    const int TB = (int)(RT / d.n);
+    const FfnNsBwd p{a.dL, a.Ap, d.A, d.n, Pa, a.Pa1, ah->off[MQ_P_FFN_W], ah->off[MQ_P_FC2_W], w.Hs, w.X1, w.dP1,
+                     a.slab_ffn, TB, ap.ns_tpa, ap.ffn_tpb};
+    hipLaunchKernelGGL(ffn_actor_ns_bwd_kernel, dim3(ap.ns_bpa, d.n), dim3(256), kFfnActorBwdLds, s, p);
+    MQ_HIP(hipGetLastError());
+    const FfnNsDw1Prob p2{d.I, w.dP1, w.XIN, a.slab_ffn, a.Pa1, d.n, ap.ns_bpa, TB, ap.ffn_tpb * FA_ROWS};
+    MQ_HIP(launch_gemm(p2, mq::H, d.I, d.n * ap.ns_bpa, s));
+    return launch_reduce(actor_reduce_plan(ap, *ah, w, a, npol), a.norm_part, "agent", s, nnorm);
+  }
   if (ap.agent == MQ_AGENT_FFN) {
     const FfnActorBwd p{a.dL, a.Ap, d.A, Pa + ah->off[MQ_P_FC2_W], Pa + ah->off[MQ_P_FFN_W], w.Hs, w.X1, w.dP1,
                         a.slab_ffn, ah->len_rnn, RT, ap.ffn_tiles, ap.ffn_tpb};

@@ -2,7 +2,7 @@
 // (Actor), its workspace rows (actor_ws_rows, probe: tests/host/actor_ws_probe.cpp), what a step launches (ActorPlan:
 // coma_plan and a2c_plan report it, actor_host.hpp launches from it) and its backward's reduction (actor_reduce_plan).
 #pragma once
-#include "ffn_actor_kernels.hpp"
+#include "ffn_actor_ns_kernels.hpp"
 #include "reduce_plan.hpp"
 
 namespace mq {
@@ -17,6 +17,10 @@ struct Actor {
   float *dL, *dHo, *pi, *ppart, *slab_fc2, *slab_ffn, *red_tmp, *norm_part;
   int ffn_slabs_max = 0, ffn_cap = 0;   // slabs slab_ffn holds; MQ_PLAN ffn_actor_blocks (0: the default cap)
   bool ffn_attr = false;   // the two ffn_actor kernels' dynamic-LDS attributes are raised
+  // the non-shared actor (MQ_AGENT_FFN_NS): ns agents of Pa1 parameters each, Pa = ns Pa1, and slab_ffn holds
+  // ffn_slabs_max whole-gradient slabs [ns][Pa1]. 0: one shared agent
+  int ns = 0;
+  int64_t Pa1 = 0;
 };
 
 struct ActorPlan {
@@ -33,7 +37,18 @@ struct ActorPlan {
   int ffn_tpb;          // tiles each of them walks (the last one the rest)
   int ffn_resident;     // 1: W1 stays in LDS, 0: streamed in K chunks
   size_t ffn_fwd_lds;   // the forward's dynamic LDS, bytes
+  // the non-shared actor (ffn_actor_ns_kernels.hpp), per agent; then ffn_tiles = n ns_tpa, ffn_blocks = n ns_bpa,
+  // ffn_fwd_blocks = n ns_fpa, ffn_tpb tiles per backward workgroup, and ns_w1 = ns_bpa
+  int ns_tpa;   // 64-row tiles of an agent's T B rows
+  int ns_bpa;   // the backward's workgroups per agent = gradient slabs = dW1 slices per agent
+  int ns_fpa;   // the forward's workgroups per agent
 };
+
+// Most backward workgroups per agent (gradient slabs) of the non-shared actor over any step of at most TBmax = T B
+// rows per agent: what slab_ffn holds. MQ_PLAN ffn_actor_blocks only lowers it.
+inline int ffn_ns_bpa_max(int64_t TBmax, int n) {
+  return (int)std::min<int64_t>(std::max(1, kFfnActorBlocks / n), std::max<int64_t>(1, (TBmax + FA_ROWS - 1) / FA_ROWS));
+}
 
 // Most workgroups (slabs) ffn_actor_bwd_kernel runs over any step with at most RTmax rows: what slab_ffn holds.
 inline int ffn_actor_blocks_max(int64_t RTmax) {
@@ -46,6 +61,21 @@ inline ActorPlan actor_plan(int I, int O, int A, int n, int R, int64_t RT, int a
   ActorPlan p{};
   p.agent = agent;
   p.ns_w1 = split_k_slices(RT, (I + Dw1Prob::BN - 1) / Dw1Prob::BN);
+  if (agent == MQ_AGENT_FFN_NS) {   // grouped: every figure per agent, over its TB = RT / n rows
+    const int64_t TB = RT / n;
+    const int cap = ffn_cap > 0 ? std::min(ffn_cap, kFfnActorBlocks) : kFfnActorBlocks;
+    p.ns_tpa = (int)std::max<int64_t>(1, (TB + FA_ROWS - 1) / FA_ROWS);
+    p.ffn_tpb = (p.ns_tpa + std::max(1, cap / n) - 1) / std::max(1, cap / n);
+    p.ns_bpa = (p.ns_tpa + p.ffn_tpb - 1) / p.ffn_tpb;   // every workgroup, and so every dW1 slice, has a tile
+    p.ns_fpa = std::min(p.ns_tpa, std::max(1, kFfnActorFwdBlocks / n));
+    p.ns_w1 = p.ns_bpa;
+    p.ffn_tiles = n * p.ns_tpa;
+    p.ffn_blocks = n * p.ns_bpa;
+    p.ffn_fwd_blocks = n * p.ns_fpa;
+    p.ffn_resident = ffn_actor_w1_resident(I) ? 1 : 0;
+    p.ffn_fwd_lds = ffn_actor_fwd_lds_bytes(I);
+    return p;
+  }
   if (agent == MQ_AGENT_FFN) {
     p.ffn_tiles = (int)((RT + FA_ROWS - 1) / FA_ROWS);
     p.ffn_fwd_blocks = std::max(1, std::min(p.ffn_tiles, kFfnActorFwdBlocks));
@@ -73,26 +103,31 @@ mq_config agent_config(const C& c, float gamma, int agent = MQ_AGENT_GRU) {
   a.obs_last_action = c.obs_last_action; a.obs_agent_id = c.obs_agent_id; a.gamma = gamma; a.lr = c.lr;
   a.optim_alpha = c.optim_alpha; a.optim_eps = c.optim_eps; a.grad_norm_clip = c.grad_norm_clip;
   a.max_batch = c.max_batch; a.max_seq = c.max_seq;
-  a.agent = agent;
+  a.agent = agent == MQ_AGENT_FFN_NS ? MQ_AGENT_FFN : agent;   // the handle lends one agent's layout
   return a;
 }
 
 // The actor's rows of a learner's workspace table, for the agent layout y and steps of at most RTmax = T R rows; the
 // capacities they give land in `a` with the pointers.
-inline WsTable actor_ws_rows(Actor& a, int A, const Layout& y, int64_t RTmax) {
+// ns > 0: the non-shared actor of ns agents (y is then one agent's layout): slab_ffn holds whole-gradient slabs and
+// red_tmp the partials of the one region they make.
+inline WsTable actor_ws_rows(Actor& a, int A, const Layout& y, int64_t RTmax, int ns = 0) {
   const int64_t l1 = (int64_t)H * y.I + H, l2 = (int64_t)A * H + A;
-  a.Pa = y.P;
+  a.ns = ns;
+  a.Pa1 = y.P;
+  a.Pa = ns > 0 ? ns * y.P : y.P;
   a.Ap = (A + 3) & ~3;
-  a.ffn_slabs_max = y.ffn ? ffn_actor_blocks_max(RTmax) : 0;
+  a.ffn_slabs_max = ns > 0 ? ffn_ns_bpa_max(RTmax / ns, ns) : y.ffn ? ffn_actor_blocks_max(RTmax) : 0;
+  const int64_t slab_len = ns > 0 ? a.Pa : y.len_rnn;
   // pass 1's partials: at most kRedZ groups of each region's length (RedBuilder::add). GRU: [dW1 | db1], the BPTT
   // slabs' W_ih .. b_hh prefix (shorter than len_rnn), [dW2 | db2], the loss sums. Feed-forward: [dW1 | db1], the whole
   // len_rnn of a [dWr | dbr | dW2 | db2] slab, the loss sums, and no region of fc2's own: the one sum covers both
-  const int64_t red_tmp = kRedZ * (l1 + y.len_rnn + l2 + MQ_NSUMS);
+  const int64_t red_tmp = kRedZ * (ns > 0 ? a.Pa + MQ_NSUMS : l1 + y.len_rnn + l2 + MQ_NSUMS);
   return {
       {"dL", RTmax * a.Ap, &a.dL}, {"dHo", RTmax * H, &a.dHo}, {"pi", RTmax * A, &a.pi},
       {"ppart", ((RTmax + 3) / 4) * MQ_NSUMS, &a.ppart},
       {"slab_fc2", kNsplitMax * l2, &a.slab_fc2},
-      {"slab_ffn", a.ffn_slabs_max * y.len_rnn, &a.slab_ffn},
+      {"slab_ffn", a.ffn_slabs_max * slab_len, &a.slab_ffn},
       {"red_tmp", red_tmp, &a.red_tmp},
       {"norm_part", kNormPartMax, &a.norm_part},
   };
@@ -102,6 +137,11 @@ inline WsTable actor_ws_rows(Actor& a, int A, const Layout& y, int64_t RTmax) {
 // and the slabs the plan's launches leave in `w` (the agent handle's workspace) and `a`. No launch, as plan_reduce.
 inline RedBuilder actor_reduce_plan(const ActorPlan& p, const Layout& y, const Work& w, const Actor& a, int npol) {
   RedBuilder rb(a.red_tmp);
+  if (p.agent == MQ_AGENT_FFN_NS) {   // one region: ns_bpa slabs, each the whole gradient [n][Pa1]
+    rb.add(a.slab_ffn, p.ns_bpa, a.Pa, a.agrad, true);
+    rb.add(a.ppart, npol, MQ_NSUMS, a.agrad + a.Pa, false);
+    return rb;
+  }
   rb.add(w.slab_fc1, p.ns_w1, (int64_t)H * y.I + H, a.agrad + y.off[MQ_P_FC1_W], true);
   if (p.agent == MQ_AGENT_FFN) {   // one slab per workgroup of ffn_actor_bwd_kernel
     rb.add(a.slab_ffn, p.ffn_blocks, y.len_rnn, a.agrad + y.off[MQ_P_FFN_W], true);

@@ -4,7 +4,8 @@
 The critic is a V network (`critic_type`: `cv_critic` on the state, `ac_critic` on the agent's own obs) trained in ONE
 optimiser step over every t against n-step returns of the target critic (`q_nstep`, `add_value_last_step`); the actor
 is the GRU agent, or under `use_rnn: False` (what epymarl's maa2c.yaml / ia2c.yaml ship) the feed-forward agent as two
-fused kernels (pymarl_amd/csrc/ffn_actor_kernels.hpp), with a softmax policy (`agent_output_type: pi_logits`, `action_selector: soft_policies`, no epsilon
+fused kernels (pymarl_amd/csrc/ffn_actor_kernels.hpp), or under `agent: rnn_ns` with `mac: non_shared_mac`
+one feed-forward agent per agent index as their grouped forms (ffn_actor_ns_kernels.hpp), with a softmax policy (`agent_output_type: pi_logits`, `action_selector: soft_policies`, no epsilon
 floor), trained with the advantage td = (return - V) mask and an entropy bonus (`entropy_coef`). All of train() is one
 launch sequence of hand-written HIP kernels (include/ma_a2c.h, pymarl_amd/csrc/a2c_kernels.hpp); torch only owns the
 buffers. There is no CPU path. One synchronisation per train(): the stats read-back that says whether the batch had a
@@ -103,7 +104,8 @@ def make_a2c_config(args, ac, input_dim, critic, max_batch, max_seq, gpow):
     cfg.gamma_pow = gpow.ctypes.data
     cfg.max_batch = int(max_batch)
     cfg.max_seq = int(max_seq)
-    cfg.agent = agent_kind(args)   # use_rnn: False selects the feed-forward actor
+    # use_rnn: False selects the feed-forward actor, agent: rnn_ns one such actor per agent
+    cfg.agent = _lib.AGENT_FFN_NS if getattr(args, "agent", "rnn") == "rnn_ns" else agent_kind(args)
     return cfg
 
 
@@ -115,6 +117,10 @@ class ActorCriticLearner:
         if getattr(mac.agent, "use_rnn", True) != use_rnn_config(args):
             raise ValueError("use_rnn: {} but the MAC's agent is {}: build the MAC from the same args.".format(
                 use_rnn_config(args), "the GRU agent" if getattr(mac.agent, "use_rnn", True) else "the feed-forward one"))
+        self.non_shared = getattr(args, "agent", "rnn") == "rnn_ns"
+        if bool(getattr(mac.agent, "non_shared", False)) != self.non_shared:
+            raise ValueError("agent: {} but the MAC's agent is {}: build the MAC from the same args.".format(
+                getattr(args, "agent", "rnn"), "non-shared" if getattr(mac.agent, "non_shared", False) else "shared"))
         self.n_agents = args.n_agents
         self.n_actions = args.n_actions
         self.mac = mac
@@ -138,7 +144,7 @@ class ActorCriticLearner:
         self.target_mode, self.target_value = self.cfg.target
         self.standardise_rewards = self.cfg.standardise_rewards
         self._gpow = gamma_table(args.gamma, self.cfg.q_nstep)
-        dev = self.mac.agent.fc1.weight.device
+        dev = next(self.mac.agent.parameters()).device
         self._agent, self.n_agent_params = pack([self.mac.agent], device=dev)
         self._critic, self.n_critic_params = pack([self.critic], device=dev)
         self._tcritic, _ = pack([self.target_critic], device=dev)
@@ -180,9 +186,11 @@ class ActorCriticLearner:
         if self._handle is None or self._handle_key[0] < need_b or self._handle_key[1] < T:
             cfg = make_a2c_config(self.args, self.cfg, self.mac.agent.input_dim, self.critic, need_b, T, self._gpow)
             h = _lib.A2CHandle(cfg)
-            if h.agent_offsets[-1] != self.n_agent_params or h.critic_offsets[-1] != self.n_critic_params:
+            # agent_offsets describe one agent's block; the non-shared actor's buffer holds n_agents of them
+            Pa = h.agent_offsets[-1] * (self.n_agents if self.non_shared else 1)
+            if Pa != self.n_agent_params or h.critic_offsets[-1] != self.n_critic_params:
                 raise _lib.MQError("parameter layout mismatch: library ({}, {}) vs modules ({}, {})".format(
-                    h.agent_offsets[-1], h.critic_offsets[-1], self.n_agent_params, self.n_critic_params))
+                    Pa, h.critic_offsets[-1], self.n_agent_params, self.n_critic_params))
             P = _lib.ptr
             _lib.check(h.lib.ma_bind(h.h, P(self._agent), P(self._agrad), P(self._asq), P(self._critic),
                                      P(self._tcritic), P(self._cgrad), P(self._csq), P(self._stats)))

@@ -1,4 +1,6 @@
 from .rnn_agent import RNNAgent
+from .rnn_ns_agent import RNNNSAgent
 
 REGISTRY = {}
 REGISTRY["rnn"] = RNNAgent
+REGISTRY["rnn_ns"] = RNNNSAgent
