@@ -34,7 +34,7 @@ enum { MA_NSTATS = 16 };
 
 typedef struct ma_config {
   int32_t n_agents, n_actions, obs_dim, state_dim;
-  int32_t rnn_hidden_dim;          /* 64 */
+  int32_t rnn_hidden_dim;          /* 64, or 128 with agent = MQ_AGENT_FFN (epymarl's hidden_dim: 128) */
   int32_t critic_hidden;           /* 64 or 128 */
   int32_t critic_type;             /* MA_CRITIC_* */
   int32_t obs_last_action, obs_agent_id;
@@ -100,10 +100,12 @@ typedef struct ma_plan {
  * size and callers built against it need no rebuild. */
 typedef struct ma_actor {
   int32_t agent;          /* MQ_AGENT_*; the items below are 0 with the GRU agent */
-  int32_t ffn_tiles;      /* 64-row tiles of the actor's rows */
-  int32_t ffn_blocks;     /* ffn_actor_bwd_kernel's workgroups = its slabs (MQ_PLAN ffn_actor_blocks=<n> lowers the cap) */
+  int32_t ffn_tiles;      /* the backward's tiles of the actor's rows: 64-row, at rnn_hidden_dim 128 32-row */
+  int32_t ffn_blocks;     /* ffn_actor_bwd_kernel's workgroups = its slabs (MQ_PLAN ffn_actor_blocks=<n> lowers the cap);
+                             at rnn_hidden_dim 128 ffn_actor_w_bwd_kernel's */
   int32_t ffn_tiles_per_block;   /* tiles each of them walks, in order (the last one the rest) */
-  int32_t ffn_fwd_lds;    /* ffn_actor_fwd_kernel's dynamic LDS, bytes: 87040 when W1 is streamed in K chunks */
+  int32_t ffn_fwd_lds;    /* ffn_actor_fwd_kernel's dynamic LDS, bytes: 87040 when W1 is streamed in K chunks; at
+                             rnn_hidden_dim 128 ffn_actor_w_fwd_kernel's 162816 */
   /* MQ_AGENT_FFN_NS (0 otherwise): the grouped plan per agent. ffn_tiles and ffn_blocks above are then n_agents times
    * the first two, and ffn_tiles_per_block the tiles a workgroup walks of its one agent */
   int32_t ns_tiles_per_agent;    /* 64-row tiles of an agent's T * B rows */
@@ -154,6 +156,14 @@ int ma_copy_intermediate(ma_handle* h, int which, float* dst, int64_t* count, vo
 int64_t ma_actor_ns_forward_workspace(const ma_config* cfg, int32_t batch_size);
 int ma_actor_ns_forward(const float* agent, const ma_config* cfg, const mq_replay* batch, int32_t t, float* logits,
                         float* hidden, float* workspace, void* stream);
+/* One acting step of the shared feed-forward actor at rnn_hidden_dim 128 (cfg->agent = MQ_AGENT_FFN; width 64 acts
+ * through mq_mac_forward) outside train(): ffn_actor_w_fwd_kernel over the batch_size * n_agents rows of stored step
+ * t. agent: the parameters in the feed-forward order. logits [batch_size][n_agents][n_actions]; hidden
+ * [batch_size][n_agents][128], h = relu(rnn(x1)); workspace: ma_actor_forward_workspace(cfg, batch_size) floats of
+ * device memory. cfg->gamma_pow is not read. */
+int64_t ma_actor_forward_workspace(const ma_config* cfg, int32_t batch_size);
+int ma_actor_forward(const float* agent, const ma_config* cfg, const mq_replay* batch, int32_t t, float* logits,
+                     float* hidden, float* workspace, void* stream);
 int ma_last_plan(const ma_handle* h, ma_plan* out);
 int ma_last_actor(const ma_handle* h, ma_actor* out);
 

@@ -47,6 +47,7 @@ MA_EXPORTS = [
     "ma_create", "ma_destroy", "ma_param_offsets", "ma_bind", "ma_set_adam", "ma_set_reward_norm", "ma_train_step",
     "ma_update_targets", "ma_critic_forward_workspace", "ma_critic_forward", "ma_copy_intermediate", "ma_last_plan",
     "ma_set_ppo", "ma_last_actor", "ma_actor_ns_forward_workspace", "ma_actor_ns_forward",
+    "ma_actor_forward_workspace", "ma_actor_forward",
 ]
 
 # mc_allreduce_fn (include/mc_coma.h): int (*)(float* buf, int64_t count, void* stream, void* ctx)
@@ -280,6 +281,9 @@ def load(required=True):
         "ma_actor_ns_forward_workspace": ([ctypes.POINTER(MAConfig), i32], i64),
         "ma_actor_ns_forward": ([vp, ctypes.POINTER(MAConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp, vp],
                                 ctypes.c_int),
+        "ma_actor_forward_workspace": ([ctypes.POINTER(MAConfig), i32], i64),
+        "ma_actor_forward": ([vp, ctypes.POINTER(MAConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp, vp],
+                             ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

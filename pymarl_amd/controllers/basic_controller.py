@@ -7,7 +7,9 @@ step's `h = relu(rnn(x1))`, which the next step does not read.
 from the replay rows in-kernel (basic_controller.py:100-135) and runs fc1 -> GRUCell -> fc2 for every
 (episode, agent) row. For agent_output_type "pi_logits" (COMA) a second HIP kernel (`mc_policy`) applies the
 reference's -1e10 mask, softmax and epsilon floor in place (basic_controller.py:53-73); the actor-critic and PPO
-learners' MAC takes either agent there, COMA's the GRU agent only.
+learners' MAC takes either agent there, COMA's the GRU agent only. The feed-forward agent at width 128 (`hidden_dim: 128`,
+DESIGN.md §3o) steps through `ma_actor_forward` instead, one launch of the wide forward kernel over the B n rows
+(`mq_create` takes width 64 only); it serves `pi_logits` alone.
 
 A host-resident batch (the reference ParallelRunner's batch under buffer_cpu_only, parallel_runner.py:45) is read
 the reference's way: the step's rows go to the device first (basic_controller.py:105-115, `.to(self.args.device)`),
@@ -21,7 +23,7 @@ from .. import _lib
 from ..components.action_selectors import REGISTRY as action_REGISTRY
 from ..components.episode_buffer import replay_view
 from ..modules.agents import REGISTRY as agent_REGISTRY
-from ..modules.agents.rnn_agent import hidden_dim, use_rnn_config
+from ..modules.agents.rnn_agent import hidden_dim, obs_dim, use_rnn_config
 
 
 def _on_device(ep_batch):
@@ -41,6 +43,7 @@ class BasicMAC:
             raise ValueError("use_rnn: False is not supported with learner coma_learner: COMA's actor is the GRU agent")
         self.action_selector = action_REGISTRY[args.action_selector](args)
         self.hidden_states = None
+        self._ws = None
 
     def select_actions(self, ep_batch, t_ep, t_env, bs=slice(None), test_mode=False):
         agent_outputs = self._forward(ep_batch, t_ep, test_mode=test_mode)
@@ -62,9 +65,54 @@ class BasicMAC:
         return EpisodeBatch(ep_batch.scheme, ep_batch.groups, ep_batch.batch_size, Tw,
                             data=SN(transition_data=data, episode_data={}), device=device), t - t0
 
+    def _ma_config(self, agent, width):
+        """ma_config of an acting step through include/ma_a2c.h: the agent's keys; the critic's are not read."""
+        cfg = _lib.MAConfig()
+        a = self.args
+        cfg.n_agents, cfg.n_actions = a.n_agents, a.n_actions
+        cfg.obs_dim = obs_dim(a, self.agent.input_dim)
+        cfg.state_dim, cfg.rnn_hidden_dim, cfg.critic_hidden, cfg.critic_type = 1, width, 64, _lib.MA_CRITIC_CV
+        cfg.obs_last_action, cfg.obs_agent_id = int(bool(a.obs_last_action)), int(bool(a.obs_agent_id))
+        cfg.agent = agent
+        return cfg
+
+    def _forward_ma(self, ep_batch, t, test_mode, entry, cfg, flat, h):
+        """One acting step through the entry-point pair `entry` / `entry`_workspace of include/ma_a2c.h on the three
+        replay routes: the logits of the B n rows, the hidden state into `h`, then the policy (mc_policy)."""
+        if self.agent_output_type != "pi_logits":
+            raise NotImplementedError("agent_output_type {!r}".format(self.agent_output_type))
+        _lib.require_gpu(flat)
+        dev, t_run = flat.device, t
+        ep_view = ep_batch
+        if not _on_device(ep_batch):   # host-resident (buffer_cpu_only): the step's rows to the device
+            ep_view, t_run = self._device_step(ep_batch, t, dev)
+        rep, keep = replay_view(ep_view)
+        bs, n = ep_batch.batch_size, self.n_agents
+        lib = _lib.load()
+        need = getattr(lib, entry + "_workspace")(cfg, bs)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = th.empty(need, dtype=th.float32, device=dev)
+        q = th.empty(bs * n, self.args.n_actions, dtype=th.float32, device=dev)
+        _lib.check(getattr(lib, entry)(_lib.ptr(flat), cfg, rep, int(t_run), _lib.ptr(q), _lib.ptr(h),
+                                       _lib.ptr(self._ws), _lib.stream_ptr()))
+        del keep
+        avail = ep_batch["avail_actions"][:, t].to(device=dev, dtype=th.int32).contiguous()
+        eps = float(getattr(self.action_selector, "epsilon", 0.0))   # soft_policies has none: no floor
+        _lib.check(lib.mc_policy(_lib.ptr(q), _lib.ptr(avail), q.shape[0], q.shape[1], eps,
+                                 int(bool(getattr(self.args, "mask_before_softmax", True))), int(bool(test_mode)),
+                                 _lib.stream_ptr()))
+        return q.view(bs, n, -1)
+
     def _forward(self, ep_batch, t, test_mode=False):
         if self.agent_output_type not in ("q", "pi_logits"):
             raise NotImplementedError("agent_output_type {!r}".format(self.agent_output_type))
+        if not self.agent.use_rnn and self.agent.hidden_dim == 128:   # the wide feed-forward actor
+            flat = self.agent._flat
+            h = th.empty(ep_batch.batch_size, self.n_agents, 128, dtype=th.float32, device=flat.device)
+            out = self._forward_ma(ep_batch, t, test_mode, "ma_actor_forward", self._ma_config(_lib.AGENT_FFN, 128),
+                                   flat, h)
+            self.hidden_states = h
+            return out
         dev = self.agent.fc1.weight.device
         _lib.require_gpu(self.agent.fc1.weight)
         t_run = t

@@ -60,6 +60,15 @@ int ma_check_config(const ma_config& c, bool train) {
   return MQ_OK;
 }
 
+// The agent's width: 64, or 128 with the shared feed-forward actor alone (ffn_actor_w_kernels.hpp).
+int ma_check_width(const ma_config& c) {
+  if (c.rnn_hidden_dim == mq::H || (c.rnn_hidden_dim == mq::HW && c.agent == MQ_AGENT_FFN)) return MQ_OK;
+  if (c.rnn_hidden_dim == mq::HW)
+    return set_err(MQ_ERR_ARG, "rnn_hidden_dim 128 needs agent = MQ_AGENT_FFN: the GRU and the non-shared actors are "
+                               "built at 64 only");
+  return set_err(MQ_ERR_ARG, "rnn_hidden_dim must be 64, or 128 with agent = MQ_AGENT_FFN");
+}
+
 ADims ma_dims(const ma_config& c, int B, int t_len, int t_stride) {
   ADims d{};
   d.n = c.n_agents; d.A = c.n_actions; d.O = c.obs_dim; d.S = c.state_dim;
@@ -198,6 +207,25 @@ int ma_gate_apply(const ma_handle* h, int nnorm_c, int nnorm_a, int64_t adam_ste
   return MQ_OK;
 }
 
+// One acting step's arguments (ma_actor_ns_forward, ma_actor_forward), before any HIP call.
+int ma_act_check(const std::string& who, const ma_config& c, const mq_replay* batch, int32_t t, int agent,
+                 const char* agent_name) {
+  int rc = ma_check_config(c, false);
+  if (rc) return rc;
+  if (c.agent != agent) return set_err(MQ_ERR_ARG, who + ": agent must be " + agent_name);
+  if (!batch->obs || !batch->actions || !batch->filled)
+    return set_err(MQ_ERR_ARG, who + ": batch needs obs, actions and filled");
+  if (batch->batch_size < 1 || batch->t_len < 1 || batch->t_len > batch->t_stride)
+    return set_err(MQ_ERR_ARG, who + ": bad batch dimensions");
+  if (t < 0 || t >= batch->t_len) return set_err(MQ_ERR_ARG, who + ": t outside the batch");
+  if ((int64_t)batch->batch_size * c.n_agents >= (1LL << 31))
+    return set_err(MQ_ERR_ARG, who + ": batch too large for 32-bit row indices");
+  if ((rc = check_ids(batch))) return rc;
+  if (batch->ep_ids_host && batch->batch_size > MQ_INLINE_IDS && !batch->ep_ids)
+    return set_err(MQ_ERR_ARG, who + ": more than MQ_INLINE_IDS episodes need device ids");
+  return MQ_OK;
+}
+
 // ma_train_step after ma_set_ppo (ppo_host.hpp).
 int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStream_t s);
 
@@ -257,19 +285,7 @@ int ma_actor_ns_forward(const float* agent, const ma_config* cfg, const mq_repla
                         float* hidden, float* workspace, void* stream) {
   if (!agent || !cfg || !batch || !logits || !hidden || !workspace)
     return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: NULL pointer");
-  int rc = ma_check_config(*cfg, false);
-  if (rc) return rc;
-  if (cfg->agent != MQ_AGENT_FFN_NS) return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: agent must be MQ_AGENT_FFN_NS");
-  if (!batch->obs || !batch->actions || !batch->filled)
-    return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: batch needs obs, actions and filled");
-  if (batch->batch_size < 1 || batch->t_len < 1 || batch->t_len > batch->t_stride)
-    return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: bad batch dimensions");
-  if (t < 0 || t >= batch->t_len) return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: t outside the batch");
-  if ((int64_t)batch->batch_size * cfg->n_agents >= (1LL << 31))
-    return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: batch too large for 32-bit row indices");
-  if ((rc = check_ids(batch))) return rc;
-  if (batch->ep_ids_host && batch->batch_size > MQ_INLINE_IDS && !batch->ep_ids)
-    return set_err(MQ_ERR_ARG, "ma_actor_ns_forward: more than MQ_INLINE_IDS episodes need device ids");
+  if (const int rc = ma_act_check("ma_actor_ns_forward", *cfg, batch, t, MQ_AGENT_FFN_NS, "MQ_AGENT_FFN_NS")) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int B = batch->batch_size, n = cfg->n_agents;
   mq_config ac = agent_config(*cfg, 0.0f, cfg->agent);
@@ -290,6 +306,42 @@ int ma_actor_ns_forward(const float* agent, const ma_config* cfg, const mq_repla
   return MQ_OK;
 }
 
+int64_t ma_actor_forward_workspace(const ma_config* cfg, int32_t batch_size) {
+  if (!cfg || batch_size < 1) return -1;
+  const int64_t I = cfg->obs_dim + (cfg->obs_last_action ? cfg->n_actions : 0) + (cfg->obs_agent_id ? cfg->n_agents : 0);
+  const int64_t rows = (int64_t)batch_size * cfg->n_agents;
+  return align_up(rows * mq::HW) + align_up(rows * I);   // X1, XIN
+}
+
+int ma_actor_forward(const float* agent, const ma_config* cfg, const mq_replay* batch, int32_t t, float* logits,
+                     float* hidden, float* workspace, void* stream) {
+  if (!agent || !cfg || !batch || !logits || !hidden || !workspace)
+    return set_err(MQ_ERR_ARG, "ma_actor_forward: NULL pointer");
+  if (const int rc = ma_act_check("ma_actor_forward", *cfg, batch, t, MQ_AGENT_FFN, "MQ_AGENT_FFN")) return rc;
+  if (cfg->rnn_hidden_dim != mq::HW)
+    return set_err(MQ_ERR_ARG, "ma_actor_forward: rnn_hidden_dim must be 128 (width 64 acts through mq_mac_forward)");
+  hipStream_t s = (hipStream_t)stream;
+  const int B = batch->batch_size, n = cfg->n_agents;
+  mq_config ac = agent_config(*cfg, 0.0f, cfg->agent);
+  ac.max_batch = B;
+  ac.max_seq = 2;
+  const Layout y = make_layout(ac, mq::HW);
+  const Dims d = mq::make_dims(ac, B, 1, batch->t_stride);
+  MQ_LDS(ffn_actor_w_fwd_kernel, kFfnActorWFwdLds);
+  MQ_HIP(hipFuncSetAttribute((const void*)ffn_actor_w_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)kFfnActorLdsMax));
+  float* X1 = workspace;
+  float* XIN = X1 + align_up((int64_t)B * n * mq::HW);
+  const int64_t rows = (int64_t)B * n;
+  const int ntiles = (int)((rows + FW_ROWS - 1) / FW_ROWS);
+  const FfnActorWFwd p{d, make_rep(batch), agent, y.off[MQ_P_FC1_W], y.off[MQ_P_FC1_B], y.off[MQ_P_FFN_W],
+                       y.off[MQ_P_FFN_B], y.off[MQ_P_FC2_W], y.off[MQ_P_FC2_B], X1, hidden, logits, XIN, rows, ntiles, t};
+  hipLaunchKernelGGL(ffn_actor_w_fwd_kernel, dim3(std::min(ntiles, kFfnActorFwdBlocks)), dim3(256), kFfnActorWFwdLds, s,
+                     p);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
 int ma_create(const ma_config* cfg, ma_handle** out) {
   if (!cfg || !out) return set_err(MQ_ERR_ARG, "NULL argument");
   const ma_config& c = *cfg;
@@ -302,8 +354,11 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
   if (grouped && c.n_agents > (ffn_cap > 0 ? std::min(ffn_cap, kFfnActorBlocks) : kFfnActorBlocks))
     return set_err(MQ_ERR_ARG, "n_agents " + std::to_string(c.n_agents) + " exceeds the non-shared actor's workgroup " +
                                    "cap (MQ_PLAN ffn_actor_blocks)");
+  if ((rc = ma_check_width(c))) return rc;
+  const bool wide = c.rnn_hidden_dim == mq::HW;
   std::unique_ptr<ma_handle> h(new ma_handle());   // a failure below frees it and the agent handle it owns
-  const mq_config ac = agent_config(c, c.gamma_pow[1], c.agent);   // (ma_check_config: gamma_pow is not NULL)
+  mq_config ac = agent_config(c, c.gamma_pow[1], c.agent);   // (ma_check_config: gamma_pow is not NULL)
+  ac.rnn_hidden_dim = mq::H;   // the wide actor's agent handle stays at the width mq_create takes
   if ((rc = mq_create(&ac, &h->a.ah))) return rc;
   h->cfg = c;
   h->cfg.gamma_pow = nullptr;   // the caller's table is copied below and not kept
@@ -334,7 +389,8 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
       {"cred_tmp", cred_tmp, &h->cred_tmp}, {"cnorm_part", kNormPartMax, &h->cnorm_part},
       {"halt", 8, nullptr, &h->halt},
   };
-  const WsTable actor_rows = actor_ws_rows(h->a, c.n_actions, *h->a.ah, RT, grouped ? n : 0);
+  const WsTable actor_rows =
+      actor_ws_rows(h->a, c.n_actions, wide ? make_layout(ac, mq::HW) : *h->a.ah, RT, grouped ? n : 0);
   // the grouped actor's one reduction region is the whole gradient: its norm partials, with the loss sums' block
   if (grouped && (h->a.Pa + 255) / 256 + 1 > kNormPartMax)
     return set_err(MQ_ERR_ARG, "the non-shared actor's " + std::to_string(h->a.Pa) +
@@ -361,7 +417,8 @@ int ma_destroy(ma_handle* h) {
 
 int ma_param_offsets(const ma_handle* h, int64_t* agent_offsets, int64_t* critic_offsets) {
   if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
-  if (agent_offsets) (void)mq_param_offsets(h->a.ah, agent_offsets);
+  if (agent_offsets)   // the actor's own layout: the agent handle's but for the wide actor
+    for (int i = 0; i <= MQ_P_COUNT; ++i) agent_offsets[i] = h->a.y.off[i];
   if (critic_offsets)
     for (int i = 0; i <= MA_P_COUNT; ++i) critic_offsets[i] = h->coff[i];
   return MQ_OK;

@@ -46,7 +46,8 @@ inline ma_plan a2c_plan(const ma_config& c, int B, int t_len, bool reward_norm, 
   p.policy_lanes = c.n_actions;
   p.ap = (c.n_actions + 3) & ~3;
   const int I = c.obs_dim + (c.obs_last_action ? c.n_actions : 0) + (c.obs_agent_id ? c.n_agents : 0);
-  const ActorPlan ap = actor_plan(I, c.obs_dim, c.n_actions, c.n_agents, R, RT, c.agent, ffn_cap);
+  const ActorPlan ap = actor_plan(I, c.obs_dim, c.n_actions, c.n_agents, R, RT, c.agent, ffn_cap,
+                                  c.rnn_hidden_dim == HW ? HW : H);
   if (actor) *actor = ap;
   p.ns_aw1 = ap.ns_w1;
   p.ns_aw2 = ap.ns_w2;

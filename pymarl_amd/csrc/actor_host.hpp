@@ -1,7 +1,9 @@
 // The launches of the policy-gradient actor the COMA, actor-critic and PPO learners share (actor_plan.hpp describes
-// it): the agent handle a.ah lends the layout, the kernels and the workspace, a.agent are the parameters. Which kernels
-// and how many slices is ActorPlan's answer; the policy kernel between forward and backward is its learner's.
+// it): the agent handle a.ah lends the kernels and the workspace, a.y is the layout (the handle's own, but for the wide
+// feed-forward actor, which also brings its own [RT][128] rows), a.agent are the parameters. Which kernels and how many
+// slices is ActorPlan's answer; the policy kernel between forward and backward is its learner's.
 #pragma once
+#include "a2c_kernels.hpp"
 #include "actor_plan.hpp"
 #include "gru_fwd_fused.hpp"
 #include "gru_kernels.hpp"
@@ -24,11 +26,16 @@ int actor_prepare(Actor& a, const ActorPlan& ap, const char* exceeds) {
     return set_err(MQ_ERR_STATE, exceeds);
   if (ap.agent != MQ_AGENT_FFN && !grouped) return MQ_OK;
   if (ap.ffn_fwd_lds > kFfnActorLdsMax) return set_err(MQ_ERR_ARG, "the feed-forward actor's forward exceeds the LDS");
-  const void* fwd = grouped ? (const void*)ffn_actor_ns_fwd_kernel : (const void*)ffn_actor_fwd_kernel;
-  const void* bwd = grouped ? (const void*)ffn_actor_ns_bwd_kernel : (const void*)ffn_actor_bwd_kernel;
-  if (const int rc = lds_fits(fwd, ap.ffn_fwd_lds, grouped ? "ffn_actor_ns_fwd_kernel" : "ffn_actor_fwd_kernel"))
+  const bool wide = ap.width == mq::HW;
+  const void* fwd = grouped ? (const void*)ffn_actor_ns_fwd_kernel
+                            : wide ? (const void*)ffn_actor_w_fwd_kernel : (const void*)ffn_actor_fwd_kernel;
+  const void* bwd = grouped ? (const void*)ffn_actor_ns_bwd_kernel
+                            : wide ? (const void*)ffn_actor_w_bwd_kernel : (const void*)ffn_actor_bwd_kernel;
+  if (const int rc = lds_fits(fwd, ap.ffn_fwd_lds, grouped ? "ffn_actor_ns_fwd_kernel"
+                                                            : wide ? "ffn_actor_w_fwd_kernel" : "ffn_actor_fwd_kernel"))
     return rc;
-  if (const int rc = lds_fits(bwd, kFfnActorBwdLds, grouped ? "ffn_actor_ns_bwd_kernel" : "ffn_actor_bwd_kernel"))
+  if (const int rc = lds_fits(bwd, wide ? kFfnActorWBwdLds : kFfnActorBwdLds,
+                              grouped ? "ffn_actor_ns_bwd_kernel" : wide ? "ffn_actor_w_bwd_kernel" : "ffn_actor_bwd_kernel"))
     return rc;
   if (!a.ffn_attr) {   // a handle has one agent kind: these are its two kernels
     MQ_HIP(hipFuncSetAttribute(fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFfnActorLdsMax));
@@ -60,6 +67,9 @@ ActorStep make_actor_step(const Actor& a, const ActorPlan& ap, const Rep& rp, in
   const Dims d = mq::make_dims(a.ah->cfg, B, T, t_stride);
   ActorStep st{ap, d, rp, make_lay(a.ah), a.ah->w, (int64_t)T * d.R};
   st.w.dHo = a.dHo;
+  if (ap.width == mq::HW) {   // the wide actor's rows are its own: the agent handle's are sized for width H
+    st.w.X1 = a.X1w; st.w.Hs = a.Hw; st.w.dP1 = a.dP1w; st.w.slab_fc1 = a.slab_w1;
+  }
   return st;
 }
 
@@ -67,7 +77,7 @@ ActorStep make_actor_step(const Actor& a, const ActorPlan& ap, const Rep& rp, in
 // (ffn_actor_fwd_kernel: X1, Hh = w.Hs, the logits and XIN).
 int actor_forward(const Actor& a, const ActorStep& st, hipStream_t s) {
   const auto& [ap, d, rp, L, w, RT] = st;
-  const int64_t* off = a.ah->off;
+  const int64_t* off = a.y.off;
   const float* Pa = a.agent;
   if (ap.agent == MQ_AGENT_FFN_NS) {   // grid (workgroups per agent, agent): a workgroup loads one agent's weights
     const FfnNsFwd p = ffn_ns_fwd_args(d, rp, Pa, a.Pa1, off, w.X1, w.Hs, w.Q, w.XIN, (int)(RT / d.n), 0);
@@ -75,7 +85,11 @@ int actor_forward(const Actor& a, const ActorStep& st, hipStream_t s) {
     MQ_HIP(hipGetLastError());
     return MQ_OK;
   }
-  if (ap.agent == MQ_AGENT_FFN) {
+  if (ap.agent == MQ_AGENT_FFN && ap.width == mq::HW) {
+    const FfnActorWFwd p{d, rp, Pa, off[MQ_P_FC1_W], off[MQ_P_FC1_B], off[MQ_P_FFN_W], off[MQ_P_FFN_B], off[MQ_P_FC2_W],
+                         off[MQ_P_FC2_B], w.X1, w.Hs, w.Q, w.XIN, RT, ap.ffn_fwd_tiles, 0};
+    hipLaunchKernelGGL(ffn_actor_w_fwd_kernel, dim3(ap.ffn_fwd_blocks), dim3(256), ap.ffn_fwd_lds, s, p);
+  } else if (ap.agent == MQ_AGENT_FFN) {
     const FfnActorFwd p{d, rp, Pa, off[MQ_P_FC1_W], off[MQ_P_FC1_B], off[MQ_P_FFN_W], off[MQ_P_FFN_B], off[MQ_P_FC2_W],
                         off[MQ_P_FC2_B], w.X1, w.Hs, w.Q, w.XIN, RT, ap.ffn_tiles, ap.ffn_resident};
     hipLaunchKernelGGL(ffn_actor_fwd_kernel, dim3(ap.ffn_fwd_blocks), dim3(256), ap.ffn_fwd_lds, s, p);
@@ -104,7 +118,7 @@ int actor_forward(const Actor& a, const ActorStep& st, hipStream_t s) {
 // [dWr | dbr | dW2 | db2] slab per workgroup into a.slab_ffn), the split-K [dW1 | db1], the reduction.
 int actor_backward(const Actor& a, const ActorStep& st, int npol, hipStream_t s, int* nnorm) {
   const auto& [ap, d, rp, L, w, RT] = st;
-  const mq_handle* ah = a.ah;
+  const Layout* ah = &a.y;
   const float* Pa = a.agent;
   if (ap.agent == MQ_AGENT_FFN_NS) {
     // every (slab, agent) block is written whole: [dWr .. db2] by workgroup (j, g), [dW1 | db1] by slice (g, j)
@@ -115,6 +129,16 @@ int actor_backward(const Actor& a, const ActorStep& st, int npol, hipStream_t s,
     MQ_HIP(hipGetLastError());
     const FfnNsDw1Prob p2{d.I, w.dP1, w.XIN, a.slab_ffn, a.Pa1, d.n, ap.ns_bpa, TB, ap.ffn_tpb * FA_ROWS};
     MQ_HIP(launch_gemm(p2, mq::H, d.I, d.n * ap.ns_bpa, s));
+    return launch_reduce(actor_reduce_plan(ap, *ah, w, a, npol), a.norm_part, "agent", s, nnorm);
+  }
+  if (ap.agent == MQ_AGENT_FFN && ap.width == mq::HW) {
+    const FfnActorWBwd p{a.dL, a.Ap, d.A, Pa + ah->off[MQ_P_FC2_W], Pa + ah->off[MQ_P_FFN_W], w.Hs, w.X1, w.dP1,
+                         a.slab_ffn, ah->len_rnn, RT, ap.ffn_tiles, ap.ffn_tpb};
+    hipLaunchKernelGGL(ffn_actor_w_bwd_kernel, dim3(ap.ffn_blocks), dim3(256), kFfnActorWBwdLds, s, p);
+    MQ_HIP(hipGetLastError());
+    // [dW1 | db1] [128][I]: the critic's weight-gradient policy, two row tiles, into Dw1Prob's slab scheme
+    const A2cDwProb<128> p2{w.dP1, mq::HW, w.XIN, d.I, d.I, w.slab_fc1, RT, ap.ns_w1};
+    MQ_HIP(launch_gemm(p2, mq::HW, d.I, ap.ns_w1, s));
     return launch_reduce(actor_reduce_plan(ap, *ah, w, a, npol), a.norm_part, "agent", s, nnorm);
   }
   if (ap.agent == MQ_AGENT_FFN) {

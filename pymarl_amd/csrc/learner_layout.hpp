@@ -10,6 +10,7 @@ namespace mq {
 
 struct Layout {
   int I = 0, E = 0, NH = 0;   // as every step's Dims derives them
+  int Hd = H;                 // the agent's hidden width: H, or 128 for the wide feed-forward actor's own layout
   bool hyper2 = false;        // QMIX with cfg.hypernet_layers = 2
   bool ffn = false;           // cfg.agent = MQ_AGENT_FFN: the feed-forward agent
   int64_t off[MQ_P_COUNT + 1] = {};
@@ -19,13 +20,16 @@ struct Layout {
   Hyp2Lay y2{};            // hyper2: the two-layer hypernet's own offsets
 };
 
-inline Layout make_layout(const mq_config& c) {
+// Hd: the agent's hidden width. Every mq_ handle's is H; the actor-critic learner's wide feed-forward actor
+// (actor_plan.hpp) asks for its own layout at 128.
+inline Layout make_layout(const mq_config& c, int Hd = H) {
   Layout y;
+  y.Hd = Hd;
   const Dims dmax = make_dims(c, c.max_batch, c.max_seq, c.max_seq);
   y.E = dmax.E; y.I = dmax.I; y.NH = dmax.NH;
   y.hyper2 = c.mixer == MQ_MIXER_QMIX && c.hypernet_layers == 2;
   y.ffn = c.agent == MQ_AGENT_FFN;
-  const int Hd = H, n = c.n_agents, A = c.n_actions, S = c.state_dim, E = y.E, I = y.I;
+  const int n = c.n_agents, A = c.n_actions, S = c.state_dim, E = y.E, I = y.I;
   const bool ffn = y.ffn;
   int64_t sz[MQ_P_COUNT] = {};
   sz[MQ_P_FC1_W] = (int64_t)Hd * I; sz[MQ_P_FC1_B] = Hd;

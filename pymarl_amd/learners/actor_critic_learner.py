@@ -15,7 +15,9 @@ Keys: `lr` (both optimisers), `optimizer` (absent or `adam`: torch.optim.Adam wi
 keys.optimizer_config; `rmsprop`: the reference's RMSprop), `grad_norm_clip`, `target_update_interval_or_tau`
 (keys.target_update_config's rules counted in critic training steps; absent: a hard update every
 `target_update_interval`, default 200, critic training steps), `standardise_rewards` (keys.reward_norm_config),
-`hidden_dim` (the critic's width, 64 or 128), `mask_before_softmax` (default True), `use_rnn` (True, False or absent).
+`hidden_dim` (the critic's width, 64 or 128; without `rnn_hidden_dim` also the agent's, as in epymarl: 128 is built for
+the shared feed-forward actor only, DESIGN.md §3o, pymarl_amd/csrc/ffn_actor_w_kernels.hpp, and refused with ValueError
+for the GRU and the non-shared actors), `mask_before_softmax` (default True), `use_rnn` (True, False or absent).
 Refused with ValueError: `learner_dp`, `standardise_returns: True`, `obs_individual_obs: True`, a critic_type other than the
 two, and a PrioritizedReplayBuffer batch.
 """
@@ -31,7 +33,7 @@ from torch.optim import Adam, RMSprop
 
 from .. import _lib
 from ..components.episode_buffer import is_per_batch, is_replay_view, replay_view
-from ..modules.agents.rnn_agent import agent_kind, obs_dim, use_rnn_config
+from ..modules.agents.rnn_agent import agent_kind, agent_width, hidden_dim, obs_dim, use_rnn_config
 from ..modules.critics import REGISTRY as critic_REGISTRY
 from ..modules.flat import link, load_state, pack, rebind, state_buffers, state_dict_own_steps, to_current_device
 from .keys import (REW_MS_INIT, hard_target_update, load_rew_ms, optimizer_config, reward_norm_config, reward_stats,
@@ -53,7 +55,10 @@ def a2c_config(args):
     ct = getattr(args, "critic_type", None)
     if ct not in CRITIC_TYPES:
         raise ValueError("critic_type {!r} not recognised (one of {}).".format(ct, ", ".join(CRITIC_TYPES)))
-    use_rnn_config(args)   # True, False or absent: anything else is refused there
+    ffn = not use_rnn_config(args)   # True, False or absent: anything else is refused there
+    shared = getattr(args, "agent", "rnn") != "rnn_ns"
+    agent_width(args, "the GRU actor" if not ffn else "the shared actor" if shared else "agent: rnn_ns",
+                wide=ffn and shared)
     if getattr(args, "learner_dp", False):
         raise ValueError("learner_dp is not supported by ActorCriticLearner.")
     if getattr(args, "standardise_returns", False):
@@ -88,7 +93,7 @@ def make_a2c_config(args, ac, input_dim, critic, max_batch, max_seq, gpow):
     cfg.n_actions = args.n_actions
     cfg.obs_dim = obs_dim(args, input_dim)
     cfg.state_dim = critic.state_dim
-    cfg.rnn_hidden_dim = 64
+    cfg.rnn_hidden_dim = hidden_dim(args)   # the agent module's width: 128 selects the wide actor
     cfg.critic_hidden = critic.hidden_dim
     cfg.critic_type = critic.KIND
     cfg.obs_last_action = int(bool(args.obs_last_action))

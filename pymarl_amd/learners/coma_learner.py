@@ -38,7 +38,7 @@ from torch.optim import RMSprop
 
 from .. import _lib
 from ..components.episode_buffer import is_per_batch, is_replay_view, replay_view
-from ..modules.agents.rnn_agent import obs_dim, state_dim, use_rnn_config
+from ..modules.agents.rnn_agent import agent_width, obs_dim, state_dim, use_rnn_config
 from ..modules.critics.coma import COMACritic
 from ..modules.flat import link, load_state, pack, rebind, to_current_device
 from .dp import (DPCheck, SharedComm, allreduce_grad_buffer, dp_active, dp_collective, dp_world, local_shard,
@@ -80,6 +80,7 @@ class COMALearner:
             # the actor's BPTT is the GRU's (include/mc_coma.h): never train a GRU where the config asked for none
             raise ValueError("COMALearner does not support use_rnn: False (the feed-forward agent): its actor is the "
                              "GRU agent.")
+        agent_width(args, "learner: coma_learner")   # its agent handle is mq_create's: width 64 only
         self.n_agents = args.n_agents
         self.n_actions = args.n_actions
         self.mac = mac

@@ -42,7 +42,7 @@ from torch.optim import Adam, RMSprop
 from .. import _lib
 from ..components.episode_buffer import (_FIELDS, PrioritizedBatch, _field_view, is_per_batch,  # noqa: F401
                                          is_replay_view, replay_view)
-from ..modules.agents.rnn_agent import Q_TARGETS, make_config  # noqa: F401
+from ..modules.agents.rnn_agent import Q_TARGETS, agent_width, make_config  # noqa: F401
 from ..modules.flat import link, load_state, pack, rebind, state_buffers, state_dict_own_steps, to_current_device
 from .dp import (DPCheck, SharedComm, allreduce_grad_buffer, dp_active, dp_collective, dp_world, local_shard,
                  native_comm_wanted)
@@ -57,6 +57,7 @@ MIXER_IDS = {None: _lib.MIXER_NONE, "vdn": _lib.MIXER_VDN, "qmix": _lib.MIXER_QM
 class QLearner:
     def __init__(self, mac, scheme, logger, args):
         self.args = args
+        agent_width(args, "learner: q_learner")   # mq_create takes 64 only: refused here, before any library call
         self.mac = mac
         self.logger = logger
         self.params = list(mac.parameters())

@@ -6,7 +6,9 @@ runs the HIP `mq_agent_forward` kernel; inside the learner the whole unroll is f
 Opt-in `use_rnn: False` (epymarl's key): `rnn` is then `nn.Linear(64, 64)` followed by a ReLU instead of the GRUCell,
     x1 = relu(fc1(inputs));  h = relu(rnn(x1));  q = fc2(h)
 with the incoming hidden state ignored and `h` returned in its place; the state_dict is epymarl's (fc1.weight,
-fc1.bias, rnn.weight, rnn.bias, fc2.weight, fc2.bias). Without the key, or with True, nothing changes.
+fc1.bias, rnn.weight, rnn.bias, fc2.weight, fc2.bias). Without the key, or with True, nothing changes. At width 128
+(epymarl's `hidden_dim: 128`) that agent is the actor-critic and PPO learners' alone: they train it and
+`BasicMAC.forward` steps it (`ma_actor_forward`); this module's own `forward` on dense inputs is built at 64 only.
 """
 from collections import OrderedDict
 
@@ -49,6 +51,17 @@ def hidden_dim(args):
     if v is None:
         raise AttributeError("args has neither rnn_hidden_dim nor hidden_dim")
     return int(v)
+
+
+def agent_width(args, who, wide=False):
+    """hidden_dim(args), checked before any library call: 64, or where `wide` (the shared feed-forward actor of the
+    actor-critic and PPO learners) also 128. Anything else: ValueError naming the key that set it."""
+    v = hidden_dim(args)
+    if v != 64 and not (wide and v == 128):
+        key = "rnn_hidden_dim" if getattr(args, "rnn_hidden_dim", None) is not None else "hidden_dim"
+        raise ValueError("{}: {} is not supported by {}: the agent's width is 64, or 128 for agent: rnn under use_rnn: "
+                         "False with learner: actor_critic_learner or ppo_learner.".format(key, v, who))
+    return v
 
 
 def agent_kind(args):
@@ -140,6 +153,10 @@ class RNNAgent(FlatModule):
     def forward(self, inputs, hidden_state=None):
         if isinstance(inputs, (dict, OrderedDict)):
             inputs = inputs["1d"]
+        if self.hidden_dim != 64:   # the inference handle is mq_create's (width 64); there is no eager path
+            raise NotImplementedError("RNNAgent.forward on dense inputs is built at width 64 only: at hidden_dim {} "
+                                      "BasicMAC.forward runs the wide forward kernel (ma_actor_forward) on the "
+                                      "batch".format(self.hidden_dim))
         _lib.require_gpu(inputs)
         x = inputs.reshape(-1, self.input_dim).float().contiguous()
         q = th.empty(x.shape[0], self.args.n_actions, dtype=th.float32, device=x.device)
