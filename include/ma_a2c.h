@@ -129,6 +129,17 @@ int ma_set_adam(ma_handle* h, const ma_adam* a);
 int ma_set_reward_norm(ma_handle* h, double* state);
 /* NULL switches back to the one-step actor-critic. Arguments are checked before any HIP call (MQ_ERR_ARG). */
 int ma_set_ppo(ma_handle* h, const ma_ppo* p);
+/* TD(lambda) critic targets in the n-step return's place: the reference's build_td_lambda_targets per
+ * agent with the target critic's V' in the target Q's place, ret_T = V'_T (1 - sum_t term_t), ret_t = (td_lambda gamma)
+ * ret_{t+1} + mask_t (r_t + ((1 - td_lambda) gamma) V'_{t+1} (1 - term_t)); both constants are formed in double from
+ * the two floats and rounded to float once. ret - V is then the GAE(lambda) advantage. Sticky, like ma_set_ppo;
+ * td_lambda < 0 switches back to the n-step return; q_nstep and add_value_last_step are not read while it is on.
+ * 0 <= td_lambda <= 1 and 0 <= gamma <= 1 are checked before any HIP call (MQ_ERR_ARG), as is the handle's max_seq
+ * against the LDS one episode's scan needs (max_seq (n_agents + 3) floats of 64 KB). */
+int ma_set_td_lambda(ma_handle* h, float td_lambda, float gamma);
+/* The returns the last ma_train_step formed: 0 the n-step return, 1 the lambda-return; -1 for a NULL handle or before
+ * the first step. */
+int ma_last_returns(const ma_handle* h);
 /* One train() on `batch` (t_len = max_t_filled). adam_step: the 1-based number of the Adam step this call applies
  * (ignored under RMSprop); the caller counts it, because a batch whose mask is empty applies nothing: it leaves every
  * bound buffer but stats untouched and writes stats[5] = 0, which the caller reads. After ma_set_ppo the call applies
@@ -144,7 +155,8 @@ int ma_update_targets(ma_handle* h, double tau, void* stream);
 int64_t ma_critic_forward_workspace(const ma_config* cfg, int32_t batch_size, int32_t t_count);
 int ma_critic_forward(const float* critic, const ma_config* cfg, const mq_replay* batch, int32_t t, float* v_out,
                       float* workspace, void* stream);
-/* 0 = V' (target critic) [T + 1][B*n]; 1 = V [T][B*n]; 2 = n-step returns [T][B*n]; 3 = pi [T][B*n][A];
+/* 0 = V' (target critic) [T + 1][B*n]; 1 = V [T][B*n]; 2 = the returns (n-step, or after ma_set_td_lambda the
+ * lambda-returns) [T][B*n]; 3 = pi [T][B*n][A];
  * 4 = dLoss/dlogits before the 1 / M scale [T * B*n][Ap], Ap = n_actions rounded up to 4 (pad columns zero).
  * After a PPO step 1, 3 and 4 hold the last epoch's values, and 5 = old, epoch 0's log pi_u [T][B*n];
  * 6 = the last epoch's ratio [T][B*n]. */

@@ -47,7 +47,7 @@ MA_EXPORTS = [
     "ma_create", "ma_destroy", "ma_param_offsets", "ma_bind", "ma_set_adam", "ma_set_reward_norm", "ma_train_step",
     "ma_update_targets", "ma_critic_forward_workspace", "ma_critic_forward", "ma_copy_intermediate", "ma_last_plan",
     "ma_set_ppo", "ma_last_actor", "ma_actor_ns_forward_workspace", "ma_actor_ns_forward",
-    "ma_actor_forward_workspace", "ma_actor_forward",
+    "ma_actor_forward_workspace", "ma_actor_forward", "ma_set_td_lambda", "ma_last_returns",
 ]
 
 # mc_allreduce_fn (include/mc_coma.h): int (*)(float* buf, int64_t count, void* stream, void* ctx)
@@ -278,6 +278,8 @@ def load(required=True):
         "ma_last_plan": ([vp, ctypes.POINTER(MAPlan)], ctypes.c_int),
         "ma_last_actor": ([vp, ctypes.POINTER(MAActor)], ctypes.c_int),
         "ma_set_ppo": ([vp, ctypes.POINTER(MAPpo)], ctypes.c_int),
+        "ma_set_td_lambda": ([vp, ctypes.c_float, ctypes.c_float], ctypes.c_int),
+        "ma_last_returns": ([vp], ctypes.c_int),
         "ma_actor_ns_forward_workspace": ([ctypes.POINTER(MAConfig), i32], i64),
         "ma_actor_ns_forward": ([vp, ctypes.POINTER(MAConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp, vp],
                                 ctypes.c_int),

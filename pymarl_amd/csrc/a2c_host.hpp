@@ -7,6 +7,7 @@
 
 #include "../../include/ma_a2c.h"
 #include "a2c_kernels.hpp"
+#include "a2c_lambda_kernels.hpp"
 #include "actor_host.hpp"
 #include "ppo_kernels.hpp"
 
@@ -32,6 +33,11 @@ struct ma_handle {
   double* rew_state = nullptr;
   bool ppo = false;   // ma_set_ppo: ma_train_step runs pp.epochs epochs (ppo_host.hpp)
   ma_ppo pp{};
+  float td_lambda = -1.0f;   // ma_set_td_lambda: -1 the n-step return
+  float lam_lg = 0.0f, lam_og = 0.0f;   // lambda gamma, (1 - lambda) gamma
+  int lam_cap = 0;           // MQ_PLAN lambda_episodes
+  A2cLambdaPlan lam{};       // the step's lambda-return launch (ma_step_plan), read by ma_returns
+  int last_returns = -1;     // ma_last_returns: 0 the n-step return, 1 the lambda-return
   ma_plan last{};
   ma_actor last_ffn{};
   int last_T = 0, last_R = 0;
@@ -158,7 +164,8 @@ int ma_critic_l12(const float* P, const int64_t* off, const ADims& d, const floa
 }
 
 // The returns: the rewards standardised first when asked for (reward[:, :T], all B T values; the statistics as they
-// were go to rbak, since an empty batch puts them back and so merges nothing into them), then the n-step pass.
+// were go to rbak, since an empty batch puts them back and so merges nothing into them), then the n-step pass, or
+// after ma_set_td_lambda the lambda-return pass in its place (h->lam: ma_step_plan's).
 int ma_returns(const ma_handle* h, const ADims& cd, const Rep& rp, const ma_plan& pl, hipStream_t s) {
   const ma_config& c = h->cfg;
   if (h->rew_state) {
@@ -167,9 +174,13 @@ int ma_returns(const ma_handle* h, const ADims& cd, const Rep& rp, const ma_plan
     hipLaunchKernelGGL(reward_norm_kernel, dim3(1), dim3(RN_THREADS), 0, s, dr, rp, h->rew_state, h->RS);
     MQ_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(a2c_nstep_kernel, dim3(cd.B), dim3(256), pl.nstep_lds, s, cd, rp, (const float*)h->Vt,
-                     (const float*)(h->rew_state ? h->RS : nullptr), (const float*)h->gpow, (int)c.q_nstep,
-                     (int)(c.add_value_last_step != 0), h->ret);
+  const float* rs = h->rew_state ? h->RS : nullptr;
+  if (h->td_lambda >= 0.0f)
+    hipLaunchKernelGGL(a2c_lambda_kernel, dim3(h->lam.grid), dim3(64 * h->lam.epw), h->lam.lds, s, cd, rp,
+                       (const float*)h->Vt, rs, h->lam_lg, h->lam_og, (int)h->lam.epw, h->ret);
+  else
+    hipLaunchKernelGGL(a2c_nstep_kernel, dim3(cd.B), dim3(256), pl.nstep_lds, s, cd, rp, (const float*)h->Vt, rs,
+                       (const float*)h->gpow, (int)c.q_nstep, (int)(c.add_value_last_step != 0), h->ret);
   MQ_HIP(hipGetLastError());
   return MQ_OK;
 }
@@ -186,6 +197,10 @@ int ma_step_plan(ma_handle* h, const mq_replay* batch, const Rep& rp, ma_plan* p
   if (const int rc = actor_prepare(h->a, ap, exceeds)) return rc;
   if (a2c_nstep_lds_bytes(Tp, h->cfg.n_agents) > kA2cNstepLdsMax)
     return set_err(MQ_ERR_ARG, "episode too long for the LDS n-step return pass");
+  if (h->td_lambda >= 0.0f) {
+    h->lam = a2c_lambda_plan(B, Tp, h->cfg.n_agents, h->lam_cap);
+    if (h->lam.epw == 0) return set_err(MQ_ERR_ARG, "episode too long for the LDS lambda-return pass");
+  }
   *act = make_actor_step(h->a, ap, rp, B, Tp - 1, batch->t_stride);   // the actor unrolls t < T only
   return MQ_OK;
 }
@@ -373,6 +388,7 @@ int ma_create(const ma_config* cfg, ma_handle** out) {
   h->ns_max = a2c_ns_max(RT);
   h->ndv_max = (int)((RT + A2C_DV_ROWS - 1) / A2C_DV_ROWS);
   h->a.ffn_cap = ffn_cap;
+  h->lam_cap = plan_int("lambda_episodes", 0);
   const int64_t lw1 = (int64_t)Hc * h->K + Hc, lw2 = (int64_t)Hc * Hc + Hc, lw3 = Hc + 1;
   const int64_t cred_tmp = kRedZ * (lw1 + lw2 + lw3 + 8);
   float* rbak_f = nullptr;
@@ -456,6 +472,28 @@ int ma_set_reward_norm(ma_handle* h, double* state) {
   return MQ_OK;
 }
 
+int ma_set_td_lambda(ma_handle* h, float td_lambda, float gamma) {
+  // the arguments first and the handle after them: none of this is a HIP call
+  const bool on = !(td_lambda < 0.0f);
+  if (on && !(td_lambda <= 1.0f))
+    return set_err(MQ_ERR_ARG, "ma_set_td_lambda: td_lambda must be in [0, 1], or < 0 for the n-step return");
+  if (on && !(gamma >= 0.0f && gamma <= 1.0f)) return set_err(MQ_ERR_ARG, "ma_set_td_lambda: gamma must be in [0, 1]");
+  if (!h) return set_err(MQ_ERR_ARG, "ma_set_td_lambda: NULL handle");
+  if (!on) {   // back to the n-step return
+    h->td_lambda = -1.0f;
+    return MQ_OK;
+  }
+  if (a2c_lambda_plan(h->cfg.max_batch, h->cfg.max_seq, h->cfg.n_agents, h->lam_cap).epw == 0)
+    return set_err(MQ_ERR_ARG, "max_seq " + std::to_string(h->cfg.max_seq) + " needs more than " +
+                                   std::to_string(kA2cNstepLdsMax) + " B of LDS for the lambda-return pass");
+  h->td_lambda = td_lambda;
+  h->lam_lg = (float)((double)td_lambda * (double)gamma);   // as step_launch.hpp forms td_lambda_kernel's
+  h->lam_og = (float)((1.0 - (double)td_lambda) * (double)gamma);
+  return MQ_OK;
+}
+
+int ma_last_returns(const ma_handle* h) { return h && h->last_T > 0 ? h->last_returns : -1; }
+
 int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void* stream) {
   if (!h || !h->a.agent) return set_err(MQ_ERR_STATE, "ma_train_step before ma_bind");
   const Actor& a = h->a;
@@ -525,6 +563,7 @@ int ma_train_step(ma_handle* h, const mq_replay* batch, int64_t adam_step, void*
   if ((rc = ma_gate_apply(h, nnorm_c, nnorm_a, adam_step, s))) return rc;
   h->last = pl;
   h->last_ffn = a2c_actor_report(act.ap);
+  h->last_returns = h->td_lambda >= 0.0f ? 1 : 0;
   h->last_T = T;
   h->last_R = R;
   return MQ_OK;

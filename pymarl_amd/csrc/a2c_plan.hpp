@@ -18,6 +18,23 @@ inline int a2c_k(const ma_config& c) {
 
 inline size_t a2c_nstep_lds_bytes(int Tp, int n) { return (size_t)Tp * (n + 2) * sizeof(float); }
 
+// a2c_lambda_kernel's launch (a2c_lambda_kernels.hpp): a wave per episode out of its own t_len (n + 3) floats of LDS,
+// four episodes a workgroup; where four do not fit kA2cNstepLdsMax two, then one. epw = 0: one episode does not fit,
+// and the step is refused. cap: MQ_PLAN lambda_episodes (1 or 2 lowers the four; anything else leaves them).
+struct A2cLambdaPlan {
+  int32_t epw;    // episodes (= waves) per workgroup: 4, 2, 1, or 0
+  int32_t grid;   // workgroups: ceil(B / epw)
+  int32_t lds;    // dynamic LDS, bytes: epw t_len (n + 3) floats
+};
+
+inline A2cLambdaPlan a2c_lambda_plan(int B, int t_len, int n, int cap = 0) {
+  const size_t wave = (size_t)t_len * (n + 3) * sizeof(float);
+  int epw = cap == 1 || cap == 2 ? cap : 4;
+  while (epw > 0 && epw * wave > kA2cNstepLdsMax) epw >>= 1;
+  if (epw == 0) return A2cLambdaPlan{0, 0, 0};
+  return A2cLambdaPlan{epw, (B + epw - 1) / epw, (int32_t)(epw * wave)};
+}
+
 // Upper bound of the split-K slices of any step with at most RTmax rows (ffn_wr_ns_max's bound: split_k_slices only
 // ever rounds this number down).
 inline int a2c_ns_max(int64_t RTmax) { return (int)std::min<int64_t>(kNsplitMax, std::max<int64_t>(1, RTmax / 256)); }

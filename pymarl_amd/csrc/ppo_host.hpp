@@ -1,8 +1,9 @@
 // Host side of the PPO step (include/ma_a2c.h ma_set_ppo): ma_train_step as E epochs over one batch,
 // in one launch sequence. What does not change between the epochs is launched once: the critic inputs X, the target
-// critic's V', the standardised rewards, the n-step returns, and the copies an empty batch puts back. An epoch is the
-// actor-critic step's remainder (a2c_host.hpp) with ppo_policy_kernel in a2c_policy_kernel's place and the online
-// critic's forward as one CLinProbT launch per layer: A2cLin2's tile code, so V is bitwise what that launch gives.
+// critic's V', the standardised rewards, the returns (n-step, or after ma_set_td_lambda the lambda-returns of
+// a2c_lambda_kernel), and the copies an empty batch puts back. An epoch is the actor-critic step's remainder
+// (a2c_host.hpp) with ppo_policy_kernel in a2c_policy_kernel's place and the online critic's forward as one CLinProbT
+// launch per layer: A2cLin2's tile code, so V is bitwise what that launch gives.
 #pragma once
 #include "a2c_host.hpp"
 
@@ -73,6 +74,7 @@ int ma_ppo_train(ma_handle* h, const mq_replay* batch, int64_t adam_step, hipStr
   pl.hoisted = hoisted;
   h->last = pl;
   h->last_ffn = a2c_actor_report(act.ap);
+  h->last_returns = h->td_lambda >= 0.0f ? 1 : 0;
   h->last_T = T;
   h->last_R = R;
   return MQ_OK;

@@ -17,7 +17,10 @@ keys.optimizer_config; `rmsprop`: the reference's RMSprop), `grad_norm_clip`, `t
 `target_update_interval`, default 200, critic training steps), `standardise_rewards` (keys.reward_norm_config),
 `hidden_dim` (the critic's width, 64 or 128; without `rnn_hidden_dim` also the agent's, as in epymarl: 128 is built for
 the shared feed-forward actor only, DESIGN.md §3o, pymarl_amd/csrc/ffn_actor_w_kernels.hpp, and refused with ValueError
-for the GRU and the non-shared actors), `mask_before_softmax` (default True), `use_rnn` (True, False or absent).
+for the GRU and the non-shared actors), `mask_before_softmax` (default True), `use_rnn` (True, False or absent),
+`q_targets` (absent or `one_step`: the n-step return; `td_lambda`: TD(lambda) critic targets with `td_lambda` in [0, 1]
+and `gamma`, DESIGN.md §3p, pymarl_amd/csrc/a2c_lambda_kernels.hpp: the return minus V is then the GAE(lambda)
+advantage, and `q_nstep` / `add_value_last_step` are not read).
 Refused with ValueError: `learner_dp`, `standardise_returns: True`, `obs_individual_obs: True`, a critic_type other than the
 two, and a PrioritizedReplayBuffer batch.
 """
@@ -33,7 +36,7 @@ from torch.optim import Adam, RMSprop
 
 from .. import _lib
 from ..components.episode_buffer import is_per_batch, is_replay_view, replay_view
-from ..modules.agents.rnn_agent import agent_kind, agent_width, hidden_dim, obs_dim, use_rnn_config
+from ..modules.agents.rnn_agent import Q_TARGETS, agent_kind, agent_width, hidden_dim, obs_dim, use_rnn_config
 from ..modules.critics import REGISTRY as critic_REGISTRY
 from ..modules.flat import link, load_state, pack, rebind, state_buffers, state_dict_own_steps, to_current_device
 from .keys import (REW_MS_INIT, hard_target_update, load_rew_ms, optimizer_config, reward_norm_config, reward_stats,
@@ -51,7 +54,8 @@ def gamma_table(gamma, q_nstep):
 
 def a2c_config(args):
     """The learner's own keys, checked: a namespace of critic_type, q_nstep, add_value_last_step, entropy_coef,
-    mask_before_softmax, optimizer (name, Adam kwargs or None), target (mode, value), standardise_rewards."""
+    mask_before_softmax, optimizer (name, Adam kwargs or None), target (mode, value), standardise_rewards, td_lambda
+    (None: the n-step return; a float in [0, 1] under q_targets: td_lambda)."""
     ct = getattr(args, "critic_type", None)
     if ct not in CRITIC_TYPES:
         raise ValueError("critic_type {!r} not recognised (one of {}).".format(ct, ", ".join(CRITIC_TYPES)))
@@ -74,6 +78,17 @@ def a2c_config(args):
     ec = getattr(args, "entropy_coef", 0.01)
     if isinstance(ec, bool) or not isinstance(ec, (int, float, np.floating)) or not float(ec) >= 0.0:
         raise ValueError("entropy_coef must be a number >= 0, got {!r}.".format(ec))
+    # opt-in TD(lambda) critic targets, through the Q learners' keys: q_targets: td_lambda selects them
+    # with args.td_lambda. Without it args.td_lambda is ignored, as there: COMA-style configs carry it globally
+    qt, lam = getattr(args, "q_targets", "one_step"), None
+    if qt not in Q_TARGETS:
+        raise ValueError("q_targets {} not recognised (one of {}).".format(qt, ", ".join(Q_TARGETS)))
+    if qt == "td_lambda":
+        lam = getattr(args, "td_lambda", None)
+        if isinstance(lam, bool) or not isinstance(lam, (int, float, np.floating, np.integer)) or \
+                not 0.0 <= float(lam) <= 1.0:
+            raise ValueError("td_lambda must be a number in [0, 1] under q_targets: td_lambda, got {!r}.".format(lam))
+        lam = float(lam)
     name = getattr(args, "optimizer", None)
     if name is None:   # epymarl's learner steps Adam: the absent key is adam here, not the Q learner's rmsprop
         name, kw = optimizer_config(SimpleNamespace(**dict(vars(args), optimizer="adam")))
@@ -84,7 +99,7 @@ def a2c_config(args):
                            entropy_coef=float(ec),
                            mask_before_softmax=bool(getattr(args, "mask_before_softmax", True)),
                            optimizer=(name, kw), target=target_update_config(args),
-                           standardise_rewards=reward_norm_config(args))
+                           standardise_rewards=reward_norm_config(args), td_lambda=lam)
 
 
 def make_a2c_config(args, ac, input_dim, critic, max_batch, max_seq, gpow):
@@ -206,6 +221,8 @@ class ActorCriticLearner:
                 _lib.check(h.lib.ma_set_adam(h.h, ctypes.byref(ad)))
             if self.rew_ms is not None:
                 _lib.check(h.lib.ma_set_reward_norm(h.h, _lib.ptr(self.rew_ms)))
+            if self.cfg.td_lambda is not None:
+                _lib.check(h.lib.ma_set_td_lambda(h.h, self.cfg.td_lambda, float(self.args.gamma)))
             self._handle, self._handle_key = h, (need_b, T)
         return self._handle
 
@@ -297,8 +314,12 @@ class ActorCriticLearner:
         _lib.check(self._handle.lib.ma_last_actor(self._handle.h, ctypes.byref(fp)))
         return dict(pl.as_dict(), **fp.as_dict())
 
+    def last_returns(self):
+        """The returns the last train() formed (ma_last_returns): 0 the n-step return, 1 the lambda-return."""
+        return int(self._handle.lib.ma_last_returns(self._handle.h))
+
     def last_intermediate(self, which):
-        """0: V' (B, T+1, n); 1: V (B, T, n); 2: the n-step returns (B, T, n); 3: pi (B, T, n, A); 4: dLoss/dlogits
+        """0: V' (B, T+1, n); 1: V (B, T, n); 2: the returns, n-step or lambda (B, T, n); 3: pi (B, T, n, A); 4: dLoss/dlogits
         before the 1 / M scale, (B, T, n, A)."""
         B, Tp = self._last_batch
         T, n, A = Tp - 1, self.n_agents, self.n_actions
