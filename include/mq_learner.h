@@ -22,6 +22,8 @@
  *   mq_agent_forward     RNNAgent.forward(inputs, hidden_state)          src/modules/agents/rnn_agent.py:27-36
  *   mq_greedy_actions    EpsilonGreedyActionSelector greedy branch      src/components/action_selectors.py:44-62
  *   mq_qmix_forward      QMixer.forward(agent_qs, states)                src/modules/mixers/qmix.py:28-47
+ *   mq_set_dmaq          (opt-in, not in the reference) pymarl2's QPLEX mixer, mixer: dmaq (DMAQer), in QMixer's place;
+ *                        mq_dmaq_forward is DMAQer.forward outside train()
  *   mq_replay.ep_ids     ReplayBuffer.sample -> EpisodeBatch.__getitem__ gather, episode_buffer.py:165-217,291-298
  *                        (ids drawn on the host exactly as the reference does; the gather is fused into kernels)
  */
@@ -34,7 +36,7 @@
 extern "C" {
 #endif
 
-enum { MQ_MIXER_NONE = 0, MQ_MIXER_VDN = 1, MQ_MIXER_QMIX = 2 };
+enum { MQ_MIXER_NONE = 0, MQ_MIXER_VDN = 1, MQ_MIXER_QMIX = 2, MQ_MIXER_DMAQ = 3 };
 enum { MQ_OK = 0, MQ_ERR_ARG = 1, MQ_ERR_HIP = 2, MQ_ERR_STATE = 3 };
 enum { MQ_NSUMS = 8 };   /* tail of the gradient buffer: sum (td*m)^2 (Huber: sum huber(td*m)), sum m, sum |td*m|, sum Q_tot*m, sum y*m */
 enum { MQ_NSTATS = 8 };  /* loss, grad_norm, td_error_abs, q_taken_mean, target_mean, mask_sum, clip coefficient,
@@ -309,6 +311,42 @@ int mq_qmix_forward2(const float* mixer, int32_t n_agents, int32_t state_dim, in
                      int32_t hypernet_embed, const float* agent_qs, const float* states, float* q_tot, int32_t rows,
                      void* stream);
 
+/* QPLEX (pymarl2's mixer: dmaq, DMAQer with adv_hypernet_layers = 1 and is_stop_gradient = True), an opt-in the
+ * reference lacks: mq_config.mixer = MQ_MIXER_DMAQ. Per live transition, with state s, chosen q_i, per-agent
+ * m_i = max over available actions of the same network's Q (the rest at -9999999) and joint one-hot action u [n A]:
+ *   w = |W2w relu(W1w s + b1w) + b2w| + 1e-10,  v = W2v relu(W1v s + b1v) + b2v        (both [n], hidden hypernet_embed)
+ *   weighted_head: q'_i = w_i q_i + v_i, m'_i = w_i m_i + v_i;  otherwise q' = q, m' = m
+ *   key_k = |Wk_k s + bk_k| + 1e-10,  ag_k = sigmoid(Wa_k s + ba_k),  ac_k = sigmoid(Wu_k [s; u] + bu_k)   (k < num_kernel)
+ *   lambda_i = sum_k key_k ag_k,i ac_k,i
+ *   Q_tot = sum_i q'_i + sum_i stopgrad(q'_i - m'_i) (lambda_i - 1)          (is_minus_one; otherwise times lambda_i)
+ * The online side takes the taken actions and the online Q's max; the target side (double_q) the target network's Q at
+ * the online argmax, that argmax as u and the target network's own max, through the target mixer. Targets, mask, the
+ * masked L2 / Huber loss, the five stats and everything from the BPTT on are the other mixers'.
+ *
+ * The mixer's parameters are ONE block of the flat buffer behind the agent's, in DMAQer.parameters() order:
+ *   hyper_w_final.0.weight [He][S], .0.bias, hyper_w_final.2.weight [n][He], .2.bias, V.0 / V.2 likewise, then
+ *   si_weight.key_extractors.k (weight [1][S], bias [1]) for every k, .agents_extractors.k ([n][S], [n]) for every k,
+ *   .action_extractors.k ([n][S + n A], [n]) for every k.
+ * mq_param_offsets reports the block's start as MQ_P_HW1_W; every other mixer entry is empty (offset = total).
+ *
+ * mq_create does not allocate a DMAQ handle's workspace: the block's size depends on mq_dmaq, so mq_set_dmaq must
+ * follow it, once, before mq_param_offsets and mq_bind (MQ_ERR_STATE after mq_bind, and at a step without it).
+ * MQ_ERR_ARG: num_kernel outside [1, MQ_DMAQ_KERNEL_MAX], hypernet_embed outside [1, MQ_HYPERNET_EMBED_MAX],
+ * n_agents above MQ_DMAQ_AGENTS_MAX (the tail's agent lanes gather n action weights per head each), a handle of
+ * another mixer. At the step: TD(lambda), a prioritized-replay step, reward standardisation and data parallelism are
+ * MQ_ERR_ARG (not supported with this mixer). */
+enum { MQ_DMAQ_KERNEL_MAX = 16, MQ_DMAQ_AGENTS_MAX = 32 };
+typedef struct mq_dmaq { int32_t num_kernel, hypernet_embed, weighted_head, is_minus_one; } mq_dmaq;
+int mq_set_dmaq(mq_handle* h, const mq_dmaq* q);
+/* DMAQer.forward(agent_qs, states, actions, max_q_i, is_v) outside train(): mixer = the module's parameters in
+ * parameters() order, agent_qs / max_q_i [rows][n_agents], states [rows][state_dim], actions [rows][n_agents *
+ * n_actions] (the joint one-hot; any floats are taken as they are), out [rows]: V_tot = sum_i q'_i when is_v != 0
+ * (actions and max_q_i are not read and may be NULL), else A_tot. The range checks are mq_set_dmaq's; MQ_ERR_ARG too
+ * when the LDS staging of four rows, 16 (state_dim + n_agents n_actions) bytes, and the kernel's own 2 KB pass 64 KB. */
+int mq_dmaq_forward(const float* mixer, const mq_dmaq* q, int32_t n_agents, int32_t n_actions, int32_t state_dim,
+                    const float* agent_qs, const float* states, const float* actions, const float* max_q_i,
+                    int32_t is_v, float* out, int32_t rows, void* stream);
+
 /* Which kernel variants the last mq_forward_backward launched (test / profiling introspection; no device sync).
  * rw_fwd / rw_bwd: rows per workgroup of the unfused recurrences (0 when the fused kernel ran). */
 enum { MQ_HYP_NONE = 0, MQ_HYP_WS = 1, MQ_HYP_LDS = 2, MQ_HYP_GEMM = 3 };
@@ -347,6 +385,10 @@ int32_t mq_last_hyper_layers(const mq_handle* h);
  * backward: ffn_kernels.hpp); bits 1 and 2 are reserved for a fused forward / backward kernel (never set by this
  * library). After such a step mq_plan.fused_fwd, rw_fwd, fused_bwd, rw_bwd, tiles, bwd_lean and dwh are all 0. */
 int32_t mq_last_agent(const mq_handle* h);
+/* The mixer of the last mq_forward_backward, an entry of its own (mq_plan keeps its size): MQ_MIXER_*; -1: NULL handle,
+ * or no forward/backward has run. After a DMAQ step (MQ_MIXER_DMAQ) mq_plan.hyper, mix and dwh are 0: the step ran
+ * DmaqL1Prob, dmaq_mix_kernel and DmaqDwProb (dmaq_kernels.hpp) in the hypernet's, the tail's and dW_hyper's place. */
+int32_t mq_last_mixer(const mq_handle* h);
 
 /* Optional per-kernel HIP-event timing of train steps (bench / profiling): events bracket every phase whose bit
  * is set in phase_mask (bit i = phase i of mq_phase_names), in a ring of `slots` steps; slots = 0 turns it off. */

@@ -11,7 +11,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MQ_LEARNER_LIB", os.path.join(HERE, "lib", "libmq_learner.so"))
 
-MIXER_NONE, MIXER_VDN, MIXER_QMIX = 0, 1, 2
+MIXER_NONE, MIXER_VDN, MIXER_QMIX, MIXER_DMAQ = 0, 1, 2, 3
 AGENT_GRU, AGENT_FFN, AGENT_FFN_NS = 0, 1, 2   # MQ_AGENT_* (AGENT_FFN_NS: ma_config.agent only)
 NSUMS = 8
 NSTATS = 8
@@ -33,7 +33,7 @@ EXPORTS = [
     "mq_greedy_actions", "mq_set_timing", "mq_phase_times", "mq_phase_names", "mq_set_data_parallel",
     "mq_last_plan", "mq_qmix_forward", "mq_qmix_forward2", "mq_last_hyper_layers", "mq_per_sample", "mq_set_per",
     "mq_set_adam", "mq_opt_step", "mq_adam_update", "mq_set_soft_target", "mq_last_soft_target", "mq_soft_update",
-    "mq_set_reward_norm", "mq_last_reward_norm", "mq_last_agent",
+    "mq_set_reward_norm", "mq_last_reward_norm", "mq_last_agent", "mq_set_dmaq", "mq_dmaq_forward", "mq_last_mixer",
     # include/mc_coma.h
     "mc_create", "mc_destroy", "mc_param_offsets", "mc_bind", "mc_train_step", "mc_update_targets", "mc_policy",
     "mc_copy_intermediate", "mc_set_timing", "mc_phase_times", "mc_last_critic_path", "mq_comm_unique_id", "mq_comm_attach",
@@ -177,6 +177,13 @@ class MQAdam(ctypes.Structure):
                 ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float), ("step", ctypes.c_int64)]
 
 
+class MQDmaq(ctypes.Structure):
+    """mq_dmaq: the QPLEX mixer's shape and switches (mq_set_dmaq, mq_dmaq_forward)."""
+    _fields_ = [("num_kernel", ctypes.c_int32), ("hypernet_embed", ctypes.c_int32),
+                ("weighted_head", ctypes.c_int32), ("is_minus_one", ctypes.c_int32)]
+
+
+DMAQ_KERNEL_MAX, DMAQ_AGENTS_MAX = 16, 32   # MQ_DMAQ_KERNEL_MAX, MQ_DMAQ_AGENTS_MAX
 PER_MAX_LIVE = 32768   # MQ_PER_MAX_LIVE: live episodes one mq_per_sample draw supports
 
 
@@ -238,6 +245,9 @@ def load(required=True):
         "mq_set_reward_norm": ([vp, vp], ctypes.c_int),
         "mq_last_reward_norm": ([vp], i32),
         "mq_last_agent": ([vp], i32),
+        "mq_last_mixer": ([vp], i32),
+        "mq_set_dmaq": ([vp, ctypes.POINTER(MQDmaq)], ctypes.c_int),
+        "mq_dmaq_forward": ([vp, ctypes.POINTER(MQDmaq), i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp], ctypes.c_int),
         "mc_critic_forward_workspace": ([ctypes.POINTER(MCConfig), i32, i32], i64),
         "mc_critic_forward": ([vp, ctypes.POINTER(MCConfig), ctypes.POINTER(MQReplay), i32, vp, vp, vp], ctypes.c_int),
         "mq_phase_times": ([vp, ctypes.POINTER(ctypes.c_float), i32, ctypes.POINTER(i32)], ctypes.c_int),
@@ -333,6 +343,7 @@ class _Owner:
         check(self._fn("create")(ctypes.byref(cfg), ctypes.byref(h)))
         self.h = h
         self.cfg = cfg
+        self._configure()
         offs = [(ctypes.c_int64 * (count + 1))() for _, count in self.OFFSETS]
         check(self._fn("param_offsets")(self.h, *offs))
         for (name, _), o in zip(self.OFFSETS, offs):
@@ -340,6 +351,9 @@ class _Owner:
 
     def _fn(self, name):
         return getattr(self.lib, "{}_{}".format(self.PREFIX, name))
+
+    def _configure(self):
+        """Between <PREFIX>_create and the read of the offsets: whatever a handle kind must set before its layout."""
 
     def __del__(self):
         try:
@@ -363,6 +377,14 @@ class _Owner:
 class Handle(_Owner):
     """Owner of an mq_handle (include/mq_learner.h)."""
     PREFIX, OFFSETS = "mq", (("offsets", P_COUNT),)
+
+    def __init__(self, cfg, dmaq=None):
+        self._dmaq = dmaq   # an MQDmaq for a MIXER_DMAQ handle
+        super().__init__(cfg)
+
+    def _configure(self):
+        if self._dmaq is not None:   # lays the mixer's block out, so ahead of the offsets (mq_set_dmaq)
+            check(self.lib.mq_set_dmaq(self.h, ctypes.byref(self._dmaq)))
 
     @property
     def n_params(self):

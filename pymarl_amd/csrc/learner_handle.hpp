@@ -29,6 +29,7 @@ struct LastStep {
   bool rs = false;        // it standardised the rewards (8, mq_last_reward_norm)
   int hyper_layers = 0;   // mq_last_hyper_layers
   int agent = 0;          // mq_last_agent
+  int mixer = 0;          // mq_last_mixer
   int soft = -1;          // of the last mq_apply (mq_last_soft_target); a forward/backward carries it over
 };
 
@@ -74,6 +75,9 @@ struct mq_handle : Layout {   // the layout is make_layout(cfg)
   // the step's standardised rewards, allocated by the first mq_set_reward_norm
   double* rew_state = nullptr;
   DevBuf<float> RS;
+  // the DMAQ mixer (mq_set_dmaq): its buffers Z [2][max M][NC], D [max M][ND] and U [max M][n] in one allocation
+  DevBuf<float> DQ;
+  DmaqBuf dqb{};
   int num_cu = 0;
   // timing: a ring of `slots` steps x PH_N (start, stop) event pairs; phases outside `mask` are not recorded
   int slots = 0;
@@ -132,6 +136,7 @@ int check_batch(const mq_handle* h, const mq_replay* b) {
   if (!b->obs || !b->actions || !b->avail_actions || !b->reward || !b->terminated || !b->filled)
     return set_err(MQ_ERR_ARG, "batch is missing a required field pointer");
   if (h->cfg.mixer == MQ_MIXER_QMIX && !b->state) return set_err(MQ_ERR_ARG, "QMIX needs batch.state");
+  if (h->cfg.mixer == MQ_MIXER_DMAQ && !b->state) return set_err(MQ_ERR_ARG, "the DMAQ mixer needs batch.state");
   if (b->batch_size < 1 || b->batch_size > h->cfg.max_batch)
     return set_err(MQ_ERR_ARG, "batch_size " + std::to_string(b->batch_size) + " outside [1, max_batch=" +
                                    std::to_string(h->cfg.max_batch) + "]");

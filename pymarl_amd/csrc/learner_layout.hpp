@@ -4,6 +4,7 @@
 #pragma once
 #include "host_util.hpp"
 #include "hyper2_kernels.hpp"
+#include "dmaq_kernels.hpp"
 #include "step_plan.hpp"
 
 namespace mq {
@@ -18,11 +19,14 @@ struct Layout {
   int64_t len_rnn = 0, len_mix = 0;
   int64_t pitch_rnn = 0;   // the fused BPTT's slab pitch: len_rnn rounded up to 4 floats (16-byte slab rows)
   Hyp2Lay y2{};            // hyper2: the two-layer hypernet's own offsets
+  bool dmaq = false;       // cfg.mixer = MQ_MIXER_DMAQ after mq_set_dmaq: the mixer is DMAQer's one block at MQ_P_HW1_W
+  DmaqLay dq{};            // dmaq: the block's own offsets and widths
 };
 
 // Hd: the agent's hidden width. Every mq_ handle's is H; the actor-critic learner's wide feed-forward actor
-// (actor_plan.hpp) asks for its own layout at 128.
-inline Layout make_layout(const mq_config& c, int Hd = H) {
+// (actor_plan.hpp) asks for its own layout at 128. q: the DMAQ mixer's parameters (mq_set_dmaq); without them a DMAQ
+// handle's layout is the agent alone.
+inline Layout make_layout(const mq_config& c, int Hd = H, const mq_dmaq* q = nullptr) {
   Layout y;
   y.Hd = Hd;
   const Dims dmax = make_dims(c, c.max_batch, c.max_seq, c.max_seq);
@@ -71,6 +75,11 @@ inline Layout make_layout(const mq_config& c, int Hd = H) {
     sz[MQ_P_V0_W] = (int64_t)E * S; sz[MQ_P_V0_B] = E;
     sz[MQ_P_V2_W] = E; sz[MQ_P_V2_B] = 1;
   }
+  if (c.mixer == MQ_MIXER_DMAQ && q) {   // one block under MQ_P_HW1_W; the other mixer entries stay empty
+    y.dmaq = true;
+    y.dq = make_dmaq_lay(0, S, n, A, *q);
+    sz[MQ_P_HW1_W] = y.dq.len;
+  }
   int64_t o = 0;
   for (int i = 0; i < MQ_P_COUNT; ++i) { y.off[order[i]] = o; o += sz[order[i]]; }
   y.off[MQ_P_COUNT] = o;
@@ -86,6 +95,7 @@ inline Layout make_layout(const mq_config& c, int Hd = H) {
   y.len_rnn = y.off[MQ_P_FC2_B] + A - y.off[ffn ? MQ_P_FFN_W : MQ_P_RNN_W_IH];
   y.pitch_rnn = (y.len_rnn + 3) & ~int64_t(3);
   y.len_mix = y.off[MQ_P_V2_W] - y.off[MQ_P_HW1_W];
+  y.dq.base = y.off[MQ_P_HW1_W];
   return y;
 }
 
@@ -129,6 +139,16 @@ inline WsTable mq_ws_table(const mq_config& c, const Layout& y, Work& w) {
       {"red_tmp", red_tmp, &w.red_tmp},         // two-pass reduction partials
       {"XIN", RT * y.I, &w.XIN},                // dense agent inputs
       {"S0", Mm * c.state_dim, &w.S0},          // gathered state[:, :-1] rows
+  };
+}
+
+// The DMAQ mixer's buffers for the largest batch, in one allocation of their own (mq_set_dmaq).
+inline WsTable dmaq_ws_table(const mq_config& c, const DmaqLay& y, DmaqBuf& b) {
+  const int64_t Mm = (int64_t)(c.max_seq - 1) * c.max_batch;
+  return {
+      {"Z", 2 * Mm * y.NC, &b.Z},
+      {"D", Mm * y.ND, &b.D},
+      {"U", Mm * y.n, nullptr, &b.U},   // int32
   };
 }
 

@@ -24,6 +24,8 @@
 // dx1 by the dP1 GEMM, dw1 by [dW_rnn | db_rnn] and dW1; everything from `hyper` to `apply` is untouched. (The
 // actor-critic and PPO learners run that agent as two fused launches of their own: ffn_actor_kernels.hpp.)
 //            (soft target updates, mq_set_soft_target: soft_update_kernel as the step's last launch)
+// The QPLEX mixer (mq_config.mixer = MQ_MIXER_DMAQ, mq_set_dmaq; dmaq_kernels.hpp): DmaqL1Prob in `hyper`'s place,
+// dmaq_mix_kernel in `mix`'s, DmaqDwProb in `dwh`'s; everything else is untouched.
 // Reward standardisation (mq_set_reward_norm): reward_norm_kernel ahead of `mix`, whose one-step pass and TD(lambda)
 // scan then read its output in place of the storage's rewards (epymarl_kernels.hpp).
 //
@@ -69,6 +71,17 @@ int agent_step(const mq_handle* h, const Dims& d, const Rep& rp, int32_t which, 
   return MQ_OK;
 }
 
+// mq_dmaq's ranges (mq_set_dmaq, mq_dmaq_forward).
+int check_dmaq(const mq_dmaq& q, int n_agents) {
+  if (q.num_kernel < 1 || q.num_kernel > MQ_DMAQ_KERNEL_MAX)
+    return set_err(MQ_ERR_ARG, "num_kernel must be in [1, " + std::to_string((int)MQ_DMAQ_KERNEL_MAX) + "]");
+  if (q.hypernet_embed < 1 || q.hypernet_embed > MQ_HYPERNET_EMBED_MAX)
+    return set_err(MQ_ERR_ARG, "hypernet_embed must be in [1, " + std::to_string((int)MQ_HYPERNET_EMBED_MAX) + "]");
+  if (n_agents < 1 || n_agents > MQ_DMAQ_AGENTS_MAX)
+    return set_err(MQ_ERR_ARG, "n_agents must be in [1, " + std::to_string((int)MQ_DMAQ_AGENTS_MAX) + "] with the DMAQ mixer");
+  return MQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -83,7 +96,7 @@ const char* mq_phase_names(void) { return kPhaseNames; }
 int mq_create(const mq_config* cfg, mq_handle** out) {
   if (!cfg || !out) return set_err(MQ_ERR_ARG, "NULL argument");
   const mq_config& c = *cfg;
-  if (c.mixer != MQ_MIXER_NONE && c.mixer != MQ_MIXER_VDN && c.mixer != MQ_MIXER_QMIX)
+  if (c.mixer != MQ_MIXER_NONE && c.mixer != MQ_MIXER_VDN && c.mixer != MQ_MIXER_QMIX && c.mixer != MQ_MIXER_DMAQ)
     return set_err(MQ_ERR_ARG, "Mixer " + std::to_string(c.mixer) + " not recognised.");
   if (c.rnn_hidden_dim != mq::H) return set_err(MQ_ERR_ARG, "rnn_hidden_dim must be 64");
   if (c.n_agents < 1 || c.n_agents > 64) return set_err(MQ_ERR_ARG, "n_agents must be in [1, 64]");
@@ -110,8 +123,18 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
     return set_err(MQ_ERR_ARG, "td_lambda: max_seq " + std::to_string(c.max_seq) + " needs more than " +
                                    std::to_string(kLambdaLdsMax) + " B of LDS for the TD(lambda) scan");
 
+  if (c.mixer == MQ_MIXER_DMAQ) {
+    if (c.n_agents > MQ_DMAQ_AGENTS_MAX)
+      return set_err(MQ_ERR_ARG, "n_agents must be in [1, " + std::to_string((int)MQ_DMAQ_AGENTS_MAX) + "] with the DMAQ mixer");
+    if (c.td_lambda > 0.0f || ov.lambda_path)
+      return set_err(MQ_ERR_ARG, "td_lambda is not supported with the DMAQ mixer");
+  }
   std::unique_ptr<mq_handle> h(new mq_handle(c));   // a failure below frees whatever it had allocated
   h->ov = ov;
+  if (c.mixer == MQ_MIXER_DMAQ) {   // laid out and allocated by mq_set_dmaq
+    *out = h.release();
+    return MQ_OK;
+  }
   const WsTable ws = mq_ws_table(c, *h, h->w);
   int rc = ws_carve(h->ws, ws, "workspace hipMalloc(" + std::to_string(ws_assign(ws, nullptr) * 4) + " B)");
   if (rc) return rc;
@@ -126,6 +149,25 @@ int mq_create(const mq_config* cfg, mq_handle** out) {
     h->dA1 = h->A1.p + 2 * len;
   }
   *out = h.release();
+  return MQ_OK;
+}
+
+int mq_set_dmaq(mq_handle* h, const mq_dmaq* q) {
+  if (!h || !q) return set_err(MQ_ERR_ARG, "NULL argument");
+  if (h->cfg.mixer != MQ_MIXER_DMAQ) return set_err(MQ_ERR_ARG, "mq_set_dmaq: the handle's mixer is not MQ_MIXER_DMAQ");
+  if (h->dmaq || h->on) return set_err(MQ_ERR_STATE, "mq_set_dmaq follows mq_create, once, before mq_bind");
+  if (const int rc = check_dmaq(*q, h->cfg.n_agents)) return rc;
+  const mq_config& c = h->cfg;
+  // the layout is committed (and with it h->dmaq) only once both allocations stand: a failed call can be repeated
+  const Layout y = make_layout(c, mq::H, q);
+  const WsTable ws = mq_ws_table(c, y, h->w);
+  int rc = ws_carve(h->ws, ws, "workspace hipMalloc(" + std::to_string(ws_assign(ws, nullptr) * 4) + " B)");
+  if (rc) return rc;
+  if ((rc = ws_carve(h->DQ, dmaq_ws_table(c, y.dq, h->dqb), "DMAQ workspace hipMalloc"))) {
+    h->ws = DevBuf<float>();   // sized for this mq_dmaq: a repeat may bring another
+    return rc;
+  }
+  static_cast<Layout&>(*h) = y;
   return MQ_OK;
 }
 
@@ -144,6 +186,7 @@ int mq_bind(mq_handle* h, float* online, float* target, float* grad, float* sq_a
             int32_t* cur_max) {
   // target/grad/sq_avg/stats may be NULL for an inference-only handle (mq_mac_forward / mq_agent_forward)
   if (!h || !online) return set_err(MQ_ERR_ARG, "NULL handle or online parameters in mq_bind");
+  if (h->cfg.mixer == MQ_MIXER_DMAQ && !h->dmaq) return set_err(MQ_ERR_STATE, "a DMAQ handle needs mq_set_dmaq before mq_bind");
   h->on = online; h->tg = target; h->grad = grad; h->sq = sq_avg; h->stats = stats; h->curmax_user = cur_max;
   return MQ_OK;
 }
@@ -168,6 +211,9 @@ int mq_forward_backward(mq_handle* h, const mq_replay* batch, void* stream) {
       return set_err(MQ_ERR_ARG, "mq_per.n_prio is smaller than the replay's n_episodes");
   }
   const bool rnorm = h->rew_state != nullptr;
+  if (h->cfg.mixer == MQ_MIXER_DMAQ && (per || rnorm || h->comm || h->dp))
+    return set_err(MQ_ERR_ARG, "the DMAQ mixer does not support prioritized replay, reward standardisation or data "
+                               "parallelism");
   if (rnorm && (h->comm || h->dp))
     return set_err(MQ_ERR_ARG, "reward standardisation does not support data parallelism (a communicator is attached "
                                "or mq_set_data_parallel is on): each rank would see only its shard's rewards");
@@ -178,14 +224,14 @@ int mq_forward_backward(mq_handle* h, const mq_replay* batch, void* stream) {
                                  h->hyper2 ? 2 : 1, h->cfg.agent);
   st.w.rec_coef = p.rec_coef;
   if ((rc = st.forward(p)) || (rc = st.hypernet(p)) || (rc = st.mixer_tail(p)) || (rc = st.hypernet2_backward(p)) ||
-      (rc = st.bptt(p)) || (rc = st.reduce(p)))
+      (rc = st.dmaq_backward(p)) || (rc = st.bptt(p)) || (rc = st.reduce(p)))
     return rc;
   if (h->comm) {   // native data parallelism: the whole [grads | sums] buffer, summed over the ranks in stream order
     const ncclResult_t r = ncclAllReduce(h->grad, h->grad, (size_t)(h->P + MQ_NSUMS), ncclFloat, ncclSum, h->comm, s);
     if (r != ncclSuccess) return set_err(MQ_ERR_HIP, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
   }
   h->last = LastStep{true, st.d, p.report, st.n_norm_part, p.lambda, p.per, p.hyper2, rnorm, p.hyper_layers,
-                     p.agent_report, h->last.soft};
+                     p.agent_report, h->cfg.mixer, h->last.soft};
   return MQ_OK;
 }
 
@@ -328,6 +374,8 @@ int mq_last_plan(const mq_handle* h, mq_plan* out) {
 int32_t mq_last_hyper_layers(const mq_handle* h) { return h && h->last.ran ? h->last.hyper_layers : -1; }
 
 int32_t mq_last_agent(const mq_handle* h) { return h && h->last.ran ? h->last.agent : -1; }
+
+int32_t mq_last_mixer(const mq_handle* h) { return h && h->last.ran ? h->last.mixer : -1; }
 
 int mq_set_data_parallel(mq_handle* h, int32_t on) {
   if (!h) return set_err(MQ_ERR_ARG, "NULL handle");
@@ -560,6 +608,26 @@ int mq_qmix_forward2(const float* mixer, int32_t n_agents, int32_t state_dim, in
   hipLaunchKernelGGL(qmix_forward2_kernel, dim3((rows + QMF2_ROWS - 1) / QMF2_ROWS), dim3(256), lds,
                      (hipStream_t)stream, mixer, o, (int)n_agents, (int)state_dim, agent_qs, states, q_tot,
                      (int)rows);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+int mq_dmaq_forward(const float* mixer, const mq_dmaq* q, int32_t n_agents, int32_t n_actions, int32_t state_dim,
+                    const float* agent_qs, const float* states, const float* actions, const float* max_q_i,
+                    int32_t is_v, float* out, int32_t rows, void* stream) {
+  if (!mixer || !q || !agent_qs || !states || !out || rows < 0 || (!is_v && (!actions || !max_q_i)))
+    return set_err(MQ_ERR_ARG, "bad mq_dmaq_forward args");
+  if (n_agents < 1 || n_actions < 1 || n_actions > 64 || state_dim < 1)
+    return set_err(MQ_ERR_ARG, "mq_dmaq_forward: n_agents >= 1, n_actions in [1, 64], state_dim >= 1");
+  if (const int rc = check_dmaq(*q, n_agents)) return rc;
+  if (rows == 0) return MQ_OK;
+  const size_t lds = dmaq_forward_lds(state_dim, n_agents, n_actions);
+  if (lds + DMF_STATIC_LDS > 64 * 1024)   // the staging and the kernel's static 2 KB together
+    return set_err(MQ_ERR_ARG, "mq_dmaq_forward: state_dim too large for the LDS staging");
+  MQ_LDS(dmaq_forward_kernel, lds);
+  const DmaqLay Y = make_dmaq_lay(0, state_dim, n_agents, n_actions, *q);
+  hipLaunchKernelGGL(dmaq_forward_kernel, dim3((rows + DMF_ROWS - 1) / DMF_ROWS), dim3(256), lds, (hipStream_t)stream,
+                     mixer, Y, agent_qs, states, actions, max_q_i, (int)(is_v != 0), out, (int)rows);
   MQ_HIP(hipGetLastError());
   return MQ_OK;
 }

@@ -69,6 +69,8 @@ inline RedBuilder plan_reduce(const StepPlan& p, const Dims& d, const Layout& y,
     // dW_hyper's few m-slice slabs go straight to pass 2 (they are written in the same launch as pass 1)
     rb.mix_direct = rb.add(w.slab_mix, p.nsplit_mix, y.len_mix, grad + y.off[MQ_P_HW1_W], true, 0, true);
     rb.add(w.slab_v2, p.nblk_mix, d.E + 1, grad + y.off[MQ_P_V2_W], true);
+  } else if (d.mixer == MQ_MIXER_DMAQ) {   // DMAQer's one block, from DmaqDwProb's m-slice slabs
+    rb.add(w.slab_mix, p.nsplit_mix, y.len_mix, grad + y.off[MQ_P_HW1_W], true, 0, true);
   }
   rb.add(w.loss_part, p.nblk_mix, MQ_NSUMS, grad + y.P, false);
   return rb;

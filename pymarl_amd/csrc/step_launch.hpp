@@ -74,6 +74,7 @@ struct Step {
   int hypernet(const StepPlan& p);
   int mixer_tail(const StepPlan& p);
   int hypernet2_backward(const StepPlan& p);
+  int dmaq_backward(const StepPlan& p);
   int bptt(const StepPlan& p);
   int reduce(const StepPlan& p);
 
@@ -175,6 +176,12 @@ int Step::forward(const StepPlan& p) {
 
 // The QMIX hypernet as a launch of its own (no forward carried it).
 int Step::hypernet(const StepPlan& p) {
+  if (p.dmaq) {   // every state-fed product of the DMAQ mixer, both nets (dmaq_kernels.hpp)
+    pt.begin(PH_HYP);
+    DmaqL1Prob p1{d, rp, h->dq, h->on, h->tg, h->dqb.Z, w.S0};
+    MQ_HIP(launch_gemm(p1, d.M, h->dq.NC, 2, s));
+    return MQ_OK;
+  }
   if (p.hyp_place != HYP_OWN_LAUNCH) return MQ_OK;
   pt.begin(PH_HYP);
   if (p.hyper2) {
@@ -216,6 +223,12 @@ int Step::mixer_tail(const StepPlan& p) {
   const float* const W = h->per.weights;
   float* const TDA = h->TDA;
   pt.begin(PH_MIX);
+  if (p.dmaq) {
+    hipLaunchKernelGGL(dmaq_mix_kernel, dim3(p.nblk_mix), dim3(256), 0, s, d, rp, (const float*)h->on,
+                       (const float*)h->tg, h->dq, w, h->dqb, curmax);
+    MQ_HIP(hipGetLastError());
+    return MQ_OK;
+  }
   if (rnorm) {   // the batch's rewards into the running statistics, and RS: the rewards every launch below reads
     hipLaunchKernelGGL(reward_norm_kernel, dim3(1), dim3(RN_THREADS), 0, s, d, rp, h->rew_state, h->RS.p);
     MQ_HIP(hipGetLastError());
@@ -266,6 +279,17 @@ int Step::hypernet2_backward(const StepPlan& p) {
   const int t0 = (y.nE + GBM - 1) / GBM, t1 = (y.E + GBM - 1) / GBM, t2 = (y.N1 + GBM - 1) / GBM;
   Hyp2DwProb pw{y, h->A1, h->dA1, w.dHYP, w.S0, w.slab_mix, h->len_mix, h->off[MQ_P_HW1_W], d.M, d.NH, d.S, p.ns, t0, t1};
   MQ_HIP(launch_gemm(pw, (t0 + t1 + t2) * GBM, std::max(y.He, d.S), p.ns, s));
+  return MQ_OK;
+}
+
+// The DMAQ mixer's weight and bias gradients behind its tail's D: p.ns m-slices of slab_mix (reduce() sums them).
+int Step::dmaq_backward(const StepPlan& p) {
+  if (!p.dmaq) return MQ_OK;
+  pt.begin(PH_DWH);
+  const DmaqLay& y = h->dq;
+  const int t1 = (y.NC + GBM - 1) / GBM;
+  DmaqDwProb pw{y, h->dqb.Z, h->dqb.D, w.S0, h->dqb.U, w.slab_mix, h->len_mix, d.M, p.ns, t1};
+  MQ_HIP(launch_gemm(pw, (t1 + 2) * GBM, std::max(y.SA, y.He), p.ns, s));
   return MQ_OK;
 }
 

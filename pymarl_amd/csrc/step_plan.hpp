@@ -139,6 +139,9 @@ struct StepPlan {
   // QMIX with the two-layer hypernet (hyper2_kernels.hpp): layer 1 and layer 2 forward as launches of their own
   // before the mixer tail, layer 2 backward and the weight gradients (ns m-slices into slab_mix) after it
   bool hyper2 = false;
+  // the DMAQ mixer (dmaq_kernels.hpp): layer 1 in the hypernet's place, dmaq_mix_kernel as the tail, the weight
+  // gradients as ns m-slices into slab_mix behind it
+  bool dmaq = false;
   int hyper_layers = 0;   // what mq_last_hyper_layers returns: 2 (hyper2), 1 (the one-layer hypernet), 0 (no QMIX mixer)
   int dw1_ns = 1;     // split-K slices of the dW1 GEMM (unfused BPTT)
   int nblk_mix = 1;   // the mixer tail's workgroups: slab_v2 / loss_part slabs
@@ -181,6 +184,14 @@ inline int pick_mix(const Dims& d, const PlanOverrides& o) {
   return fast && d.A <= 16 ? MQ_MIX_FAST16 : fast && d.A <= 32 ? MQ_MIX_FAST32 : stream ? MQ_MIX_STREAM : MQ_MIX_GENERIC;
 }
 
+// The DMAQ mixer of either agent kind: its own tail in `mix`'s place (no MQ_MIX_* variant), and the weight gradients'
+// m-slices, few enough to go straight to reduction pass 2.
+inline void plan_dmaq(StepPlan& p, const PlanOverrides& o, const Dims& d) {
+  p.dmaq = true;
+  p.mix = 0;
+  p.ns = p.nsplit_mix = std::max(1, std::min({o.dwh_split, kRedZ, (d.M + 1) / 2}));
+}
+
 inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims& d, bool inline_ids,
                           bool have_lambda_ws, int num_cu, bool per = false, int hyper_layers = 1,
                           int agent = MQ_AGENT_GRU) {
@@ -210,6 +221,7 @@ inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims
     p.lambda = have_lambda_ws;
     p.per = per;
     p.nblk_mix = (d.M + 3) / 4;
+    if (c.mixer == MQ_MIXER_DMAQ) plan_dmaq(p, o, d);
     p.dw1_ns = p.nsplit_fc1 = split_k_slices(RT, (d.I + Dw1Prob::BN - 1) / Dw1Prob::BN);
     p.ffn_wr_ns = split_k_slices(RT, 1);
     const int cap = o.ffn_dp2_blocks > 0 ? std::min(o.ffn_dp2_blocks, kFfnDp2Blocks) : kFfnDp2Blocks;
@@ -278,6 +290,7 @@ inline StepPlan plan_step(const mq_config& c, const PlanOverrides& o, const Dims
   p.lambda = have_lambda_ws;   // cfg.td_lambda > 0 or MQ_PLAN lambda_path=1 (mq_create)
   p.per = per;   // armed for this step (mq_set_per): changes no other choice
   p.nblk_mix = (d.M + 3) / 4;
+  if (c.mixer == MQ_MIXER_DMAQ) plan_dmaq(p, o, d);
 
   // BPTT slabs, dW1 split
   if (tiles) {

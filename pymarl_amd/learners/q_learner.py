@@ -20,6 +20,10 @@ Opt-in `use_rnn: False` (epymarl's key, modules/agents/rnn_agent.py): the agent'
 step runs the feed-forward agent's GEMM chain in the recurrence's place (ffn_kernels.hpp, mq_config.agent);
 `last_agent()` says which agent the last step ran. Without the key nothing changes.
 
+Opt-in `mixer: dmaq` (pymarl2's QPLEX, modules/mixers/dmaq.py): the step runs the DMAQ launches in the hypernet's, the
+tail's and dW_hyper's place (dmaq_kernels.hpp, mq_set_dmaq); `last_mixer()` says which mixer the last step ran. It is
+refused with q_targets: td_lambda, a PrioritizedReplayBuffer batch, learner_dp and standardise_rewards.
+
 Data parallel: with `args.learner_dp = True` and torch.distributed initialised (RCCL, one process
 per GPU), every rank calls train() with the SAME GLOBAL sample, as run.py:207-219 does unchanged (ranks share the
 seed, so the sampled ids agree; ids and contents checked on a call-count schedule, `args.learner_dp_check`); the
@@ -48,10 +52,11 @@ from .dp import (DPCheck, SharedComm, allreduce_grad_buffer, dp_active, dp_colle
                  native_comm_wanted)
 from .keys import (OPTIMIZERS, REW_MS_INIT, hard_target_update, load_rew_ms, optimizer_config,  # noqa: F401
                    reward_norm_config, reward_stats, save_rew_ms, target_update_config)
+from ..modules.mixers.dmaq import DMAQer
 from ..modules.mixers.qmix import QMixer
 from ..modules.mixers.vdn import VDNMixer
 
-MIXER_IDS = {None: _lib.MIXER_NONE, "vdn": _lib.MIXER_VDN, "qmix": _lib.MIXER_QMIX}
+MIXER_IDS = {None: _lib.MIXER_NONE, "vdn": _lib.MIXER_VDN, "qmix": _lib.MIXER_QMIX, "dmaq": _lib.MIXER_DMAQ}
 
 
 class QLearner:
@@ -73,6 +78,15 @@ class QLearner:
                 self.mixer = VDNMixer()
             elif args.mixer == "qmix":
                 self.mixer = QMixer(args)
+            elif args.mixer == "dmaq":
+                # QPLEX: refused with the opt-ins its tail does not carry, before any library call
+                if getattr(args, "q_targets", "one_step") == "td_lambda":
+                    raise ValueError("q_targets: td_lambda is not supported with mixer: dmaq")
+                if getattr(args, "learner_dp", False):
+                    raise ValueError("learner_dp is not supported with mixer: dmaq")
+                if self.standardise_rewards:
+                    raise ValueError("standardise_rewards is not supported with mixer: dmaq")
+                self.mixer = DMAQer(args)
             else:
                 raise ValueError("Mixer {} not recognised.".format(args.mixer))
             self.params += list(self.mixer.parameters())
@@ -157,7 +171,8 @@ class QLearner:
         if self._handle is None or self._handle_key[0] < need_b or self._handle_key[1] < T:
             cfg = make_config(self.args, MIXER_IDS[self.args.mixer], input_dim=self.mac.agent.input_dim,
                               max_batch=need_b, max_seq=T)
-            h = _lib.Handle(cfg)
+            # every other mixer's handle is made as it always was; dmaq's is laid out by mq_set_dmaq before the offsets
+            h = _lib.Handle(cfg, dmaq=self.mixer.dmaq_struct()) if self.args.mixer == "dmaq" else _lib.Handle(cfg)
             Tmax = T
             self._curmax = th.zeros(Tmax * need_b * self.args.n_agents, dtype=th.int32, device=self._online.device)
             _lib.check(h.lib.mq_bind(h.h, _lib.ptr(self._online), _lib.ptr(self._target), _lib.ptr(self._grad),
@@ -187,11 +202,13 @@ class QLearner:
 
     # -- reference API ---------------------------------------------------------------------------------------
     def train(self, batch, t_env: int, episode_num: int):
+        per = is_per_batch(batch)
+        if per and self.args.mixer == "dmaq":   # refused before anything else: no device is needed to say so
+            raise ValueError("a PrioritizedReplayBuffer batch is not supported with mixer: dmaq")
         _lib.require_gpu(self._online)
         # decided per call: torch.distributed may be initialised after the handle was created; mq_apply must then
         # recompute the gradient norm from the all-reduced buffer
         dp = self._dp_active()
-        per = is_per_batch(batch)
         if per and (self.dp or getattr(self, "force_dp_norm", False)):
             raise ValueError("learner_dp is not supported with a PrioritizedReplayBuffer batch: the priorities and "
                              "importance weights belong to one device's buffer")
@@ -320,6 +337,10 @@ class QLearner:
         d["mix"] = _lib.MIX_NAMES[d["mix"]]
         d["dwh"] = ("red1", "bptt_grid")[d["dwh"]]
         return d
+
+    def last_mixer(self):
+        """mq_last_mixer of the last train(): _lib.MIXER_* (MIXER_DMAQ: the step ran the QPLEX launches)."""
+        return int(self._handle.lib.mq_last_mixer(self._handle.h))
 
     def last_agent(self):
         """mq_last_agent of the last train(): 0 when the GRU agent ran; otherwise a bit set, bit 0 = the feed-forward

@@ -60,13 +60,13 @@ def make_buffer(seed=0):
     return buf, groups
 
 
-def make_learner(buf, groups, layers, seed=0):
+def make_learner(buf, groups, layers, seed=0, mixer=MIXER):
     import torch as th
     from pymarl_amd.controllers import REGISTRY as mac_REGISTRY
     from pymarl_amd.learners import REGISTRY as le_REGISTRY
     from pymarl_amd.utils.logging import Logger
     args = SN(n_agents=N_AGENTS, n_actions=N_ACTIONS, state_shape=STATE, obs_shape=OBS, rnn_hidden_dim=64,
-              mixing_embed_dim=32, mixer=MIXER, lr=5e-4, optim_alpha=0.99, optim_eps=1e-5, grad_norm_clip=10.0,
+              mixing_embed_dim=32, mixer=mixer, lr=5e-4, optim_alpha=0.99, optim_eps=1e-5, grad_norm_clip=10.0,
               gamma=0.99, double_q=True, target_update_interval=200, learner_log_interval=10 ** 12,
               obs_last_action=True, obs_agent_id=True, agent="rnn", mac="basic_mac", agent_output_type="q",
               action_selector="epsilon_greedy", epsilon_start=1.0, epsilon_finish=0.05, epsilon_anneal_time=50000,
